@@ -13,11 +13,22 @@ barrier and the max-over-ranks clock.
 
 Rank 0 prints ONE JSON line with, besides the contract's keys,
   roofline      dominant kernel: algorithmic bytes / HIP-event duration against the 8 TB/s HBM peak;
+and, with --full only,
+  config.bit_exact_vs_oracle  pictures of the last timed step against the CPU oracle (null in a plain run);
   end_to_end    SURVEY 8(d)'s definition of the metric: stream bytes in host memory -> entropy decode on the host
                 cores -> H2D -> kernels -> D2H -> planes + RGB in page-locked host memory (mvhp_engine_decode, the
                 pipeline behind minivideo_decode), with the share of each stage and which one binds;
+  engine_multi_context, cli   the single-process multi-context engine and the cold mini_thumbnailer run;
+  placement     the same launch re-timed on the other kind of buffers (--placement-trials);
   cpu_baseline  (N = 1) the CPU restatement (oracle/, kind "port") on a bounded sample: reconstruction only (the span
                 of `value`) and front end + reconstruction (the span of end_to_end), one thread and all host cores.
+A plain run (no --full) sets up, warms up, times the --steps steps and prints the line; nothing else.
+
+--dump-outputs DIR (rank 0): after the timed steps, what the last step wrote, as float32 arrays of shape
+(pictures, samples): DIR/ycbcr.npy (planar YCbCr) and DIR/rgb.npy (unless --no-rgb).  The rows are a fixed, seeded
+choice of up to 16 pictures of the batch, in ascending order; the columns a fixed, seeded choice of up to 2^18 byte
+offsets inside one picture's output, in ascending order (33.6 MB in all).  The inputs are generated from fixed seeds, so
+two runs with the same arguments -- on two builds, say -- can be compared array for array.
 """
 import argparse
 import json
@@ -40,6 +51,11 @@ BYTES_PER_MB_COLOR = 384 + 768  # colour kernel: YCbCr in + RGB out (B_rgb - B_y
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the oracle check of the last step, the end-to-end, multi-context and CLI legs, "
+                         "the placement trials and the CPU baseline (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of what the last timed step computed to DIR/*.npy (float32)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=2048, help="pictures per GPU per step (weak scaling)")
@@ -87,7 +103,10 @@ def parse_args():
                          "share them = a rehearsal, never a result).  -1: --gpus when N > 1, 2 on one GPU (rehearsal); 0: skip")
     ap.add_argument("--cli-pictures", type=int, default=999,
                     help="pictures of the cold mini_thumbnailer run (a fresh process: stream file on tmpfs -> .yuv files); 0: skip")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -482,6 +501,30 @@ def cli_cold(args, params, stream, n_distinct, rec):
         shutil.rmtree(d, ignore_errors=True)
 
 
+DUMP_SEED = 20240611
+DUMP_PICTURES = 16
+DUMP_OFFSETS = 1 << 18
+
+
+def dump_outputs(path, params, F, p_yuv, p_rgb, hipc):
+    """--dump-outputs: a fixed, seeded sample of the batch the last timed step wrote (device pointers p_yuv / p_rgb), as
+    float32 .npy files; the same sample whatever the build, for the same arguments."""
+    rng = np.random.default_rng(DUMP_SEED)
+    pics = np.sort(rng.choice(F, size=min(F, DUMP_PICTURES), replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, ptr, nbytes in (("ycbcr", p_yuv, params.yuv_bytes), ("rgb", p_rgb, params.rgb_bytes)):
+        if ptr is None:
+            continue
+        offs = np.sort(rng.choice(nbytes, size=min(nbytes, DUMP_OFFSETS), replace=False))
+        out = np.empty((len(pics), len(offs)), np.float32)
+        buf = np.empty(nbytes, np.uint8)
+        for i, f in enumerate(pics):
+            if hipc.hipMemcpy(buf.ctypes.data, ptr + int(f) * nbytes, nbytes, 2) != 0:
+                raise SystemExit("bench: reading back picture %d for --dump-outputs failed" % f)
+            out[i] = buf[offs]
+        np.save(os.path.join(path, name + ".npy"), out)
+
+
 def main():
     args = parse_args()
     env_world = os.environ.get("WORLD_SIZE")
@@ -570,16 +613,16 @@ def main():
     # like the kernel leg: weak scaling by default (2048 pictures per rank), the fixed job with --strong
     e2e_total = args.e2e_pictures if args.e2e_pictures >= 0 else (args.strong or 2048 * world)
     e2e = None
-    if e2e_total >= world and stream is not None:
+    if args.full and e2e_total >= world and stream is not None:
         e2e = end_to_end(args, params, stream, n_distinct, rec, want_rgb, e2e_total, rank, world, local_rank, dist, dev)
 
     # ---- the single-process multi-context leg and the cold CLI run (rank 0; the other ranks wait at the barrier below) ----
     multi = cli = None
-    if use_dist:
+    if args.full and use_dist:
         torch.cuda.synchronize()
         torch.cuda.empty_cache()           # rank 0's engine allocates on every device: leave it the room
         dist.barrier(group=host_pg)
-    if rank == 0 and stream is not None:
+    if args.full and rank == 0 and stream is not None:
         n_dev = torch.cuda.device_count() if not rehearsal else 1
         n_ctx = args.engine_contexts if args.engine_contexts >= 0 else (world if world > 1 else 2)
         # (two side legs: an environmental failure -- no room on the tmpfs for 6 GB of PNG files, a CLI run that hits its
@@ -595,7 +638,7 @@ def main():
                 cli = cli_cold(args, params, stream, n_distinct, rec)
             except Exception as ex:   # noqa: BLE001
                 cli = {"error": "%s: %s" % (type(ex).__name__, ex)}
-    if use_dist:
+    if args.full and use_dist:
         dist.barrier(group=host_pg)   # the other ranks start their kernel leg only when rank 0's engine has left their devices
 
     d_small = torch.from_numpy(rec.reshape(rec.shape[0], -1)).to(dev)
@@ -687,6 +730,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     hot.sync_check(sp)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, params, F, *out_sets[(launch_no[0] - 1) % len(out_sets)], hipc)   # what the last step wrote
     layout_name, waves_used = hot.last_launch()   # what the library chose (speed only)
     recon_name = {"rows": "recon_rows_kernel", "quad": "recon_quad_kernel", "oct": "recon_oct_kernel",
                   "wide": "recon_rows_kernel", "quad_wide": "recon_quad_kernel", "pipe": "recon_pipe_kernel", "pipe1": "recon_pipe1_kernel"}[layout_name]
@@ -702,25 +747,27 @@ def main():
     mbs_per_step = F * params.mbs
     value = total_frames * params.mbs * args.steps / elapsed
 
-    # spot-check pictures of the last step against the oracle (bit-exact) -- the checker, not the product
+    # (--full) spot-check pictures of the last step against the oracle (bit-exact) -- the checker, not the product
     # (every rank checks its own batch; the verdicts are reduced with MIN so that a mismatch on any rank fails the run)
-    from oracle import loader
-    ok = True
+    ok = None
     p_yuv, p_rgb = out_sets[(launch_no[0] - 1) % len(out_sets)]   # what the last step wrote
-    for f in sorted({0, 1, 2, 3, F // 2, F - 1} & set(range(F))):
-        src = f % rec.shape[0]
-        ref, ref_rgb = loader.recon(params, rec[src:src + 1], 1, want_rgb=want_rgb)
-        got = np.empty(params.yuv_bytes, np.uint8)
-        assert hipc.hipMemcpy(got.ctypes.data, p_yuv + f * params.yuv_bytes, params.yuv_bytes, 2) == 0
-        ok = ok and bool(np.array_equal(got, ref))
-        if want_rgb:
-            got = np.empty(params.rgb_bytes, np.uint8)
-            assert hipc.hipMemcpy(got.ctypes.data, p_rgb + f * params.rgb_bytes, params.rgb_bytes, 2) == 0
-            ok = ok and bool(np.array_equal(got, ref_rgb))
-    ok = all_ranks_ok(ok, world, dist, dev)
+    if args.full:
+        from oracle import loader
+        ok = True
+        for f in sorted({0, 1, 2, 3, F // 2, F - 1} & set(range(F))):
+            src = f % rec.shape[0]
+            ref, ref_rgb = loader.recon(params, rec[src:src + 1], 1, want_rgb=want_rgb)
+            got = np.empty(params.yuv_bytes, np.uint8)
+            assert hipc.hipMemcpy(got.ctypes.data, p_yuv + f * params.yuv_bytes, params.yuv_bytes, 2) == 0
+            ok = ok and bool(np.array_equal(got, ref))
+            if want_rgb:
+                got = np.empty(params.rgb_bytes, np.uint8)
+                assert hipc.hipMemcpy(got.ctypes.data, p_rgb + f * params.rgb_bytes, params.rgb_bytes, 2) == 0
+                ok = ok and bool(np.array_equal(got, ref_rgb))
+        ok = all_ranks_ok(ok, world, dist, dev)
     # The same launch on the OTHER kind of buffers, for comparison (reported beside `value`, never part of it): --placement-trials N
     placement = None
-    if world == 1 and args.placement_trials > 0:
+    if args.full and world == 1 and args.placement_trials > 0:
         keep = (p_packed, p_yuv, p_rgb)
         hold, ms_other, ms_more_ordinary = [], [], []
         other_placed = None
@@ -869,7 +916,7 @@ def main():
             "engine_multi_context": multi,
             "cli": cli,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(params, stream, n_distinct, rec, want_rgb, args.cpu_seconds)
             out["cpu_baseline"] = cb
             if e2e and "end_to_end" in cb:

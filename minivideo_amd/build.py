@@ -116,6 +116,37 @@ def build_oracle(force=False):
     return ORACLE
 
 
+STOCK_CLI = os.path.join(ROOT, "oracle", "_ref", "mini_thumbnailer_stock")
+STOCK_MAIN = os.path.join("mini_thumbnailer", "src", "main.cpp")
+
+
+def reference_dir():
+    """the upstream MiniVideo checkout, if there is one: $MINIVIDEO_REFERENCE, else the `reference_path` BASELINE.json
+    records, else reference/ beside this repository or in the home directory"""
+    import json
+    try:
+        recorded = json.load(open(os.path.join(ROOT, "BASELINE.json"))).get("reference_path")
+    except (OSError, ValueError):
+        recorded = None
+    for d in (os.environ.get("MINIVIDEO_REFERENCE"), recorded, os.path.join(os.path.dirname(ROOT), "reference"),
+              os.path.expanduser(os.path.join("~", "reference"))):
+        if d and os.path.exists(os.path.join(d, STOCK_MAIN)):
+            return os.path.abspath(d)
+    return None
+
+
+def build_stock_cli(force=False):
+    """The reference's own mini_thumbnailer front end, built unchanged against include/minivideo.h (oracle/Makefile).  Only
+    where the upstream sources are present; elsewhere a binary that came with the tree is kept as it is."""
+    ref = reference_dir()
+    if ref is None:
+        return STOCK_CLI if os.path.exists(STOCK_CLI) else None
+    if not force and not _newer(STOCK_CLI, [os.path.join(ref, STOCK_MAIN), os.path.join(ROOT, "include", "minivideo.h"), LIB]):
+        return STOCK_CLI
+    _run(["make", "-C", os.path.join(ROOT, "oracle"), "-B", "REFERENCE=" + ref, "_ref/mini_thumbnailer_stock"])
+    return STOCK_CLI
+
+
 CLI = os.path.join(PKG, "mini_thumbnailer")
 
 
@@ -133,6 +164,7 @@ def build_all(force=False):
     build_cli(force)
     build_generator(force)
     build_oracle(force)
+    build_stock_cli(force)
     return build_report(force)
 
 
@@ -141,7 +173,7 @@ def build_report(force=False):
     return {"build_mode": "forced rebuild" if force else "incremental (only what is older than its sources)",
             "build_exercised": len(COMMANDS) > 0, "commands_run": len(COMMANDS),
             "hip_objects_compiled": sum(1 for c in COMMANDS if "--offload-arch=gfx950" in c and "-c" in c),
-            "artifacts": [os.path.relpath(p, ROOT) for p in (LIB, CLI, GEN, ORACLE) if os.path.exists(p)]}
+            "artifacts": [os.path.relpath(p, ROOT) for p in (LIB, CLI, GEN, ORACLE, STOCK_CLI) if os.path.exists(p)]}
 
 
 if __name__ == "__main__":

@@ -1,21 +1,36 @@
-"""CPU, this container only: the reference's own mini_thumbnailer/src/main.cpp compiles and links,
-unchanged and in place, against include/minivideo.h + libminivideo.so (drop-in boundary, config 0
-plumbing).  Skipped where /root/reference does not exist (the GPU box)."""
+"""The drop-in boundary (config 0 plumbing): the reference's own mini_thumbnailer/src/main.cpp, compiled and linked
+unchanged against include/minivideo.h + libminivideo.so by build() (oracle/Makefile, binary in oracle/_ref/; compiled here if
+build() did not find the upstream sources and they can be found now), runs; and the
+public enums of include/minivideo.h carry the reference's values (tests/golden/reference_enums.json)."""
+import json
 import os
 import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MAIN = "/root/reference/mini_thumbnailer/src/main.cpp"
+STOCK = os.path.join(ROOT, "oracle", "_ref", "mini_thumbnailer_stock")
 
 
-@pytest.mark.skipif(not os.path.exists(MAIN), reason="reference checkout not present")
-def test_stock_mini_thumbnailer_builds_and_runs(tmp_path):
+def _stock_cli(tmp_path):
+    """the binary build() made; else, where the upstream sources can be read now, the same compile into tmp_path"""
+    if os.path.exists(STOCK):
+        return STOCK
+    from minivideo_amd import build
+    ref = build.reference_dir()
+    if ref is None:
+        pytest.skip("oracle/_ref/mini_thumbnailer_stock not built and no upstream MiniVideo checkout found "
+                    "($MINIVIDEO_REFERENCE, BASELINE.json reference_path, reference/ beside the repository or in ~)")
     exe = tmp_path / "mini_thumbnailer_stock"
+    main = os.path.join(ref, build.STOCK_MAIN)
     pkg = os.path.join(ROOT, "minivideo_amd")
-    subprocess.check_call(["g++", "-O1", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(MAIN), MAIN,
+    subprocess.check_call(["g++", "-O1", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(main), main,
                            "-L" + pkg, "-lminivideo", "-Wl,-rpath," + pkg, "-o", str(exe)])
+    return exe
+
+
+def test_stock_mini_thumbnailer_builds_and_runs(tmp_path):
+    exe = _stock_cli(tmp_path)
     kat = os.path.join(ROOT, "tests", "golden", "kat_cavlc_2mb.264")
     r = subprocess.run([str(exe), "-i", kat, "-f", "yuv420"], cwd=tmp_path, capture_output=True, text=True, timeout=60)
     assert r.returncode == 0                     # exit status reflects minivideo_close (main.cpp:285-298)
@@ -48,19 +63,17 @@ def _enums(path):
     return out
 
 
-REF_SRC = "/root/reference/minivideo/src"
+REF_ENUMS = os.path.join(ROOT, "tests", "golden", "reference_enums.json")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SRC), reason="reference checkout not present")
 def test_public_enums_have_the_reference_values(tmp_path):
     """every enum constant include/minivideo.h declares exists in the reference's public headers with the same value
     (minivideo.h:42-52 error codes, avcodecs.h picture / container / codec enums, avutils.h:143-149 extraction modes, ...);
     the three enums a thumbnailer passes or could receive are complete.  The values are asserted by the COMPILER on our header
-    (static_assert in a translation unit), the reference's are read from its headers as text (they cannot be compiled here:
-    they include a CMake-generated file)."""
-    ref = {}
-    for h in ("minivideo.h", "avcodecs.h", "avutils.h", "bitstream_map_struct.h", "mediafile_struct.h"):
-        ref.update(_enums(os.path.join(REF_SRC, h)))
+    (static_assert in a translation unit).  The reference's were read from its public headers as text (they cannot be compiled
+    on their own: they include a CMake-generated file) and are stored, complete for every enum our header declares, in
+    tests/golden/reference_enums.json."""
+    ref = json.load(open(REF_ENUMS))
     ours = _enums(os.path.join(ROOT, "include", "minivideo.h"))
     assert {"MiniVideoErrorCodes_e", "PictureFormat_e", "PictureRepartition_e"} <= set(ours)
     lines = ['#include "minivideo.h"']

@@ -4,7 +4,7 @@
 # BASELINE.json configuration.  usage (GPU box, repo root): bash tools/content_ablation.sh > gpurun_out/content_ablation.log
 R=${GRAFT_REPO_ROOT:-$PWD}
 cd $R
-Q="--no-cpu-baseline --e2e-pictures 0 --placement-trials 0 --steps 10 --warmup 2"
+Q="--full --no-cpu-baseline --e2e-pictures 0 --placement-trials 0 --steps 10 --warmup 2"
 run() {
   name=$1; shift
   out=$(timeout -k 10 200 python3 bench.py $Q "$@" 2>/dev/null) || { echo "$name FAILED"; return; }

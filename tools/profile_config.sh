@@ -12,7 +12,7 @@ OUT=$R/gpurun_out
 mkdir -p $OUT/prof_$TAG $OUT/pmc_$TAG
 export TMPDIR=/tmp
 cd $R
-python3 bench.py "$@" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 bench.py --full "$@" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 echo "bench $TAG done"
 cd /tmp
 # the traced run prints its own bench line: the same launches are behind <tag>_traced_bench.json and <tag>_kernel_stats.csv

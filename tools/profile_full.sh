@@ -12,7 +12,7 @@ OUT=$R/gpurun_out
 mkdir -p $OUT/prof_$TAG $OUT/pmc_$TAG $OUT/sq_$TAG
 export TMPDIR=/tmp
 cd $R
-timeout -k 10 400 python3 bench.py "$@" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { echo "bench $TAG failed"; tail -5 $OUT/${TAG}_bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full "$@" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { echo "bench $TAG failed"; tail -5 $OUT/${TAG}_bench.err; exit 1; }
 echo "bench $TAG done"
 cd /tmp
 QUICK="--no-cpu-baseline --e2e-pictures 0 --placement-trials 0"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box): bash tools/sweep.sh "<bench args common>" "<variant args 1>" "<variant args 2>" ...
 # runs bench.py once per variant, appends the JSON lines to gpurun_out/sweep.log
-COMMON=$1; shift
+COMMON="--full $1"; shift   # (the summary below reads config.bit_exact_vs_oracle)
 mkdir -p gpurun_out
 for v in "$@"; do
   echo "## $COMMON $v" >> gpurun_out/sweep.log

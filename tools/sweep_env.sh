@@ -1,6 +1,6 @@
 #!/bin/bash
 # like sweep.sh but each variant is "ENVVAR=value ... -- bench args"
-COMMON=$1; shift
+COMMON="--full $1"; shift   # (the summary below reads config.bit_exact_vs_oracle)
 mkdir -p gpurun_out
 for v in "$@"; do
   envpart=${v%%--*}; argpart=${v#*--}
