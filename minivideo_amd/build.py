@@ -147,6 +147,28 @@ def build_stock_cli(force=False):
     return STOCK_CLI
 
 
+REF_CLI = os.path.join(ROOT, "oracle", "_ref", "mini_thumbnailer_ref")
+
+
+def build_reference_cli(force=False):
+    """The reference decoder itself: upstream minivideo/ as a static archive + upstream mini_thumbnailer/src/main.cpp
+    (oracle/Makefile), the expected value of tests/test_reference_diff.py and tests/test_gpu_reference_diff.py.  Only where
+    the upstream sources are present; elsewhere a binary that came with the tree is kept as it is."""
+    ref = reference_dir()
+    if ref is None:
+        return REF_CLI if os.path.exists(REF_CLI) else None
+    srcs = [os.path.join(ref, STOCK_MAIN), os.path.join(ref, "minivideo", "CMakeLists.txt"),
+            os.path.join(ROOT, "oracle", "Makefile")]
+    if not force and not _newer(REF_CLI, srcs):
+        return REF_CLI
+    try:   # (needs cmake; without it the reference tests skip, saying how to build the tool, and the recorded digests stand in)
+        _run(["make", "-C", os.path.join(ROOT, "oracle"), "-B", "REFERENCE=" + ref, "_ref/mini_thumbnailer_ref"])
+    except (OSError, subprocess.CalledProcessError) as e:
+        print("build: the reference decoder was not built (%s)" % e, flush=True)
+        return None
+    return REF_CLI
+
+
 CLI = os.path.join(PKG, "mini_thumbnailer")
 
 
@@ -165,6 +187,7 @@ def build_all(force=False):
     build_generator(force)
     build_oracle(force)
     build_stock_cli(force)
+    build_reference_cli(force)
     return build_report(force)
 
 
@@ -173,7 +196,7 @@ def build_report(force=False):
     return {"build_mode": "forced rebuild" if force else "incremental (only what is older than its sources)",
             "build_exercised": len(COMMANDS) > 0, "commands_run": len(COMMANDS),
             "hip_objects_compiled": sum(1 for c in COMMANDS if "--offload-arch=gfx950" in c and "-c" in c),
-            "artifacts": [os.path.relpath(p, ROOT) for p in (LIB, CLI, GEN, ORACLE, STOCK_CLI) if os.path.exists(p)]}
+            "artifacts": [os.path.relpath(p, ROOT) for p in (LIB, CLI, GEN, ORACLE, STOCK_CLI, REF_CLI) if os.path.exists(p)]}
 
 
 if __name__ == "__main__":
