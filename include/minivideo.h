@@ -12,7 +12,9 @@
  *   - return codes SUCCESS = 1, FAILURE = 0, UNSUPPORTED = -1 (typedef.h:40-42);
  *   - minivideo_decode() writes <input basename>[_k].<ext> into the CURRENT WORKING
  *     DIRECTORY and ignores output_directory (export.c:627-642,704-708, h264.c:65);
- *   - no deblocking filter is applied; the picture is the uncropped coded size;
+ *   - no deblocking filter is applied by default; the picture is the uncropped coded size
+ *     (opt-in, outside the reference's behaviour: MINIVIDEO_DEBLOCK=1 in the environment applies the standard's in-loop
+ *     deblocking filter, clause 8.7, to Annex-B and MP4 input alike; independent of MINIVIDEO_SPEC=1);
  *   - H.264 IDR pictures only, from Annex-B elementary streams (.264/.h264 or a
  *     file starting with an SPS start code) or from the first H.264 video track
  *     of an MP4/MOV file (demuxer/mp4/mp4.c:1950 mp4_fileParse -> sync samples).

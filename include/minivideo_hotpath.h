@@ -22,6 +22,7 @@
  *                                                picture construction)
  *       export.c:65-188, export_utils.c:117-198 (planar YCbCr gather)
  *       export_utils.c:209-324                  (mb_to_rgb colour conversion)
+ *       -- plus, opt-in (MVHP_PARAM_DEBLOCK), the in-loop deblocking filter of clause 8.7, which the reference does not have.
  *
  * The packed macroblock record below is the build's replacement for the
  * reference's Macroblock_t (decoder/h264/h264_macroblock_struct.h:209-319) as
@@ -83,11 +84,16 @@ typedef struct mvhp_mb_header {
     uint8_t  cbp;              /* bits 0-3 CodedBlockPatternLuma, bits 4-5 ...Chroma            */
     uint8_t  chroma_pred_mode; /* IntraChromaPredMode 0=DC 1=H 2=V 3=Plane                      */
     uint8_t  i16_pred_mode;    /* Intra16x16PredMode 0=V 1=H 2=DC 3=Plane                       */
-    uint8_t  flags;            /* reserved (TransformBypassModeFlag is never set for 8-bit)     */
+    uint8_t  flags;            /* bits 1-2: disable_deblocking_filter_idc (0, 1, 2) of the macroblock's slice -- set only by
+                                  streams opened with MVHP_STREAM_DEBLOCK, read only under MVHP_PARAM_DEBLOCK / stage
+                                  MVHP_STAGE_DEBLOCK; bit 0: compact transfer form only ("dense", see below); bits 3-7: 0
+                                  (TransformBypassModeFlag is never set for 8-bit)                                      */
     uint8_t  unavail;          /* MVHP_UNAVAIL_*: neighbouring macroblocks that exist by geometry but lie in ANOTHER SLICE
                                   (6.4.8: not available); always 0 for the reference's one-slice pictures -- set only by
                                   streams opened with MVHP_STREAM_SPEC, announced by MVHP_PARAM_SLICES   */
-    uint8_t  reserved0;
+    uint8_t  dbk_offsets;      /* deblocking filter offsets of the macroblock's slice (MVHP_STREAM_DEBLOCK streams, else 0):
+                                  bits 0-3 slice_alpha_c0_offset_div2, bits 4-7 slice_beta_offset_div2, each a 4-bit
+                                  two's-complement value in -6..6                                                      */
     uint32_t nz_mask;          /* bit b (0-15): luma 4x4 block b (or 8x8 block b>>2) has a
                                   non-zero level; bit 16+k: Cb block k; bit 20+k: Cr block k.
                                   DC levels count for the block whose slot 0 they occupy.
@@ -100,6 +106,7 @@ typedef struct mvhp_mb_header {
 #define MVHP_UNAVAIL_B 2u   /* above       (mbAddrB) */
 #define MVHP_UNAVAIL_C 4u   /* above right (mbAddrC) */
 #define MVHP_UNAVAIL_D 8u   /* above left  (mbAddrD) */
+#define MVHP_DBK_IDC_SHIFT 1   /* mvhp_mb_header_t::flags: (flags >> MVHP_DBK_IDC_SHIFT) & 3 = disable_deblocking_filter_idc */
 
 /* ---------------------------------------------------------------------------
  * Compact pictures: the transfer format between the host front end and the GPU (PCIe carries it instead of the packed
@@ -149,6 +156,12 @@ typedef struct mvhp_stream_params {
  * MVHP_PARAM_SCALING  scaling4 / scaling8 hold non-flat weight matrices (SPS / PPS scaling lists).  Same kernel. */
 #define MVHP_PARAM_SLICES  4u
 #define MVHP_PARAM_SCALING 8u
+/* flags: apply the in-loop deblocking filter (clause 8.7) to the reconstructed pictures, with the per-macroblock
+ * disable_deblocking_filter_idc / offsets of the records (mvhp_mb_header_t::flags bits 1-2, dbk_offsets) and slice boundaries
+ * from mvhp_mb_header_t::unavail.  Set by mvhp_stream_params() for streams opened with MVHP_STREAM_DEBLOCK; callers that build
+ * records themselves may set it.  Outside the parity contract (the reference never deblocks); without it no filter is
+ * applied.  Filtered pictures are converted to RGB by the separate colour kernel, after the filter. */
+#define MVHP_PARAM_DEBLOCK 16u
 
 /* Bytes of one reconstructed picture: planar Y | Cb | Cr of the *uncropped*
  * coded size (export.c:80-81), and interleaved RGB8. */
@@ -171,6 +184,11 @@ MVHP_EXPORT int  mvhp_stream_open(const uint8_t *data, size_t size, mvhp_stream_
  * (MVHP_PARAM_SPEC_LUMA_DC); pictures of several slices (MVHP_PARAM_SLICES), SPS / PPS scaling lists (MVHP_PARAM_SCALING) and
  * I_PCM macroblocks (MVHP_KIND_IPCM) are decoded by the standard's rules. */
 #define MVHP_STREAM_SPEC 1u
+/* MVHP_STREAM_DEBLOCK (opt-in, independent of MVHP_STREAM_SPEC; also chosen by minivideo_decode when the environment has
+ * MINIVIDEO_DEBLOCK=1): the front end fills the records' deblocking fields from the slice headers (and refuses a slice whose
+ * disable_deblocking_filter_idc is above 2 or whose offsets lie outside -6..6), and mvhp_stream_params() sets
+ * MVHP_PARAM_DEBLOCK.  Without it those record bytes stay 0 and no picture is filtered. */
+#define MVHP_STREAM_DEBLOCK 2u
 MVHP_EXPORT int  mvhp_stream_open_ex(const uint8_t *data, size_t size, uint32_t flags, mvhp_stream_t **out);
 /* Same for an ISO-BMFF (MP4/MOV) buffer: avcC parameter sets + the IDR NAL units of the sync samples of the first
  * video track (replaces demuxer/mp4/mp4.c:2587 mp4_fileParse for the thumbnail path). */
@@ -210,10 +228,16 @@ MVHP_EXPORT int  mvhp_recon_batch_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_
 MVHP_EXPORT int  mvhp_expand_compact_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const void *d_compact,
                                          size_t stride, int n_pictures, void *d_packed, void *stream);
 
-/* Same, but only the stages selected by `stages` (bit 0: reconstruction kernel,
- * bit 1: colour kernel) -- lets a caller bracket each kernel with its own events. */
-#define MVHP_STAGE_RECON 1
-#define MVHP_STAGE_COLOR 2
+/* Same, but only the stages selected by `stages` -- lets a caller bracket each kernel with its own events:
+ * bit 0: reconstruction kernel (followed by the deblocking filter when p->flags has MVHP_PARAM_DEBLOCK),
+ * bit 1: colour conversion of d_yuv into d_rgb (after the filter when both run),
+ * bit 2: the deblocking filter alone, in place on d_yuv, with the record headers of d_packed and the params (whatever
+ *        p->flags says).
+ * Error word of the context (mvhp_sync_check): bit 0 a reconstruction row wait timed out, bit 1 a wide launch's ticket lay
+ * outside the launch, bit 2 a deblocking row wait timed out. */
+#define MVHP_STAGE_RECON   1
+#define MVHP_STAGE_COLOR   2
+#define MVHP_STAGE_DEBLOCK 4
 MVHP_EXPORT int  mvhp_recon_stages_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p,
                                        const void *d_packed, int n_frames,
                                        uint8_t *d_yuv, uint8_t *d_rgb, void *stream, int stages);

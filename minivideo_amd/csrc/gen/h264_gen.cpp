@@ -202,6 +202,10 @@ struct GenCfg {
     int n_slices = 1;     // slices per picture
     int pcm_permille = 0; // share of I_PCM macroblocks
     int scaling = 0;      // bit 0: scaling lists in the SPS, bit 1: in the PPS (profile 100 only)
+    // deblocking syntax (mvgen_stream_dbk; 0 = no deblocking_filter_control_present_flag, as every other stream)
+    int deblock = 0;
+    int dbk_idc_mask = 1;        // bit k: disable_deblocking_filter_idc k may be drawn for a slice
+    int dbk_off_min = 0, dbk_off_max = 0;   // slice_alpha_c0_offset_div2 / slice_beta_offset_div2 range
 };
 
 struct MbSyntax {
@@ -228,7 +232,11 @@ struct Gen {
     Rng rng;
     Maps m;
     int W, H;
-    explicit Gen(const GenCfg &c) : cfg(c), rng(c.seed), W(c.width_mbs), H(c.height_mbs) {}
+    explicit Gen(const GenCfg &c) : cfg(c), rng(c.seed), W(c.width_mbs), H(c.height_mbs), dbk_rng(c.seed ^ 0xdeb10c6f11e7ull) {}
+    // the deblocking syntax is drawn from a generator of its own: the macroblocks of a stream stay those of the same
+    // configuration without it
+    Rng dbk_rng;
+    uint8_t dbk_flags = 0, dbk_offsets = 0;   // record fields of the slice being written
 
     // ---- random syntax ----
     void rand_block(int *lev, int n, double p_coded, double geo, int first = 0)
@@ -402,6 +410,8 @@ struct Gen {
             h.mb_kind = MVHP_KIND_IPCM;
             h.qp_y = (uint8_t)s.qp;
             h.unavail = unavail_bits(mbx, mby);
+            h.flags = dbk_flags;
+            h.dbk_offsets = dbk_offsets;
             memcpy(rec, &h, sizeof(h));
             uint8_t *area = rec + MVHP_MB_HEADER_BYTES;
             for (int y = 0; y < 16; y++) memcpy(area + 64 * (y >> 1) + 16 * (y & 1), s.samples + 16 * y, 16);
@@ -451,6 +461,8 @@ struct Gen {
         h.chroma_pred_mode = (uint8_t)s.cmode;
         h.i16_pred_mode = (uint8_t)(i16 ? (s.mb_type - 1) % 4 : 0);
         h.unavail = unavail_bits(mbx, mby);
+        h.flags = dbk_flags;
+        h.dbk_offsets = dbk_offsets;
         if (!i16) for (int b = 0; b < (s.t8 ? 4 : 16); b++) h.pred_mode[b] = (uint8_t)s.pred[b];
         uint32_t nz = 0;
         for (int b = 0; b < 24; b++) {
@@ -911,7 +923,7 @@ struct Gen {
         bw.bit(0); bw.bits(0, 2);
         bw.se(0); bw.se(0);
         bw.se(cfg.cqp_offset[0]);
-        bw.bit(0);               // deblocking_filter_control_present_flag
+        bw.bit(cfg.deblock ? 1 : 0);   // deblocking_filter_control_present_flag
         bw.bit(0);               // constrained_intra_pred_flag
         bw.bit(0);               // redundant_pic_cnt_present_flag
         if (cfg.profile_idc == 100) {
@@ -953,6 +965,17 @@ struct Gen {
             bw.bits(0, 4);                     // pic_order_cnt_lsb
             bw.bit(0); bw.bit(0);              // no_output_of_prior_pics_flag, long_term_reference_flag
             bw.se(slice_qp - 26);
+            if (cfg.deblock) {
+                int idc;
+                do { idc = dbk_rng.below((cfg.dbk_idc_mask & 8) ? 4 : 3); } while (!((cfg.dbk_idc_mask >> idc) & 1));
+                const int span = cfg.dbk_off_max - cfg.dbk_off_min + 1;
+                const int oa = idc != 1 ? cfg.dbk_off_min + dbk_rng.below(span) : 0;
+                const int ob = idc != 1 ? cfg.dbk_off_min + dbk_rng.below(span) : 0;
+                bw.ue((uint32_t)idc);          // disable_deblocking_filter_idc
+                if (idc != 1) { bw.se(oa); bw.se(ob); }
+                dbk_flags = (uint8_t)(idc << MVHP_DBK_IDC_SHIFT);
+                dbk_offsets = (uint8_t)((oa & 15) | ((ob & 15) << 4));
+            }
             CabacEnc enc(bw);
             if (cfg.cabac) { while (!bw.aligned()) bw.bit(1); enc.init(slice_qp); }
             int qp_prev = slice_qp;
@@ -1038,6 +1061,34 @@ size_t mvgen_stream_ex(const mvgen_cfg_t *c, int32_t n_slices, int32_t pcm_permi
     g.n_slices = n_slices;
     g.pcm_permille = pcm_permille;
     g.scaling = scaling;
+    return run_generator(g, out, cap, packed, weights);
+}
+
+// mvgen_stream_ex plus the deblocking syntax: the PPS sets deblocking_filter_control_present_flag and every slice draws its
+// disable_deblocking_filter_idc from the set bits of idc_mask (bit k = idc k) and, unless idc = 1, both offsets (div2) from
+// [off_min, off_max] (idc_mask bit 3 and offsets outside -6..6 leave the standard's ranges) -- from a random generator of its own, so the macroblocks are those of the same configuration without it.
+// The packed records carry the fields (mvhp_mb_header_t::flags bits 1-2, dbk_offsets).
+__attribute__((visibility("default")))
+size_t mvgen_stream_dbk(const mvgen_cfg_t *c, int32_t n_slices, int32_t pcm_permille, int32_t scaling, int32_t idc_mask,
+                        int32_t off_min, int32_t off_max, uint8_t *out, size_t cap, uint8_t *packed, uint8_t *weights)
+{
+    if (!c || c->width_mbs <= 0 || c->height_mbs <= 0 || c->n_frames <= 0) return 0;
+    if (c->profile_idc != 66 && c->profile_idc != 77 && c->profile_idc != 100) return 0;
+    if (c->cabac && c->profile_idc == 66) return 0;
+    if (c->transform8x8 && c->profile_idc != 100) return 0;
+    if (scaling && c->profile_idc != 100) return 0;
+    if (n_slices < 1 || pcm_permille < 0 || pcm_permille > 1000) return 0;
+    // (idc 3 and offsets beyond -6..6 break the standard's ranges: for tests of the front end's refusal only -- the records
+    //  then hold the low bits)
+    if ((idc_mask & 15) == 0 || (idc_mask & ~15) || off_min < -12 || off_max > 12 || off_min > off_max) return 0;
+    GenCfg g = to_cfg(c);
+    g.n_slices = n_slices;
+    g.pcm_permille = pcm_permille;
+    g.scaling = scaling;
+    g.deblock = 1;
+    g.dbk_idc_mask = idc_mask;
+    g.dbk_off_min = off_min;
+    g.dbk_off_max = off_max;
     return run_generator(g, out, cap, packed, weights);
 }
 

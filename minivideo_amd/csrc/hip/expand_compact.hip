@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void expand_compact_kernel(ExpandArgs a)
     for (int i = lane; i < 200; i += 32) {
         uint32_t v = 0;
         if (i < 8 || dense) v = rec[i];
-        if (i == 1) v &= ~0x0000ff00u;
+        if (i == 1) v &= ~0x00000100u;                         // flags bit 0 ("dense"); bits 1-2 = deblocking idc
         if (i == 7) v = 0;
         t[i] = v;
     }

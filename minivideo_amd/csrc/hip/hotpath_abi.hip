@@ -386,14 +386,30 @@ static int wide_prepare(mvhp_ctx *c, mvhp::ReconArgs &a, size_t seam_bytes, uint
     return MVHP_SUCCESS;
 }
 
-static int launch_all(mvhp_ctx *c, const mvhp_stream_params_t *p, const void *d_packed, int n_frames,
-                      uint8_t *d_yuv, uint8_t *d_rgb, hipStream_t st, bool recon, bool color)
+// Meaning of the context's error word (bit 0 / 1: reconstruction kernels, bit 2: deblocking kernel)
+static const char *err_word_text(uint32_t err)
 {
+    if (err & 2u) return "a workgroup's ticket lay outside the launch";
+    if (err & 1u) return "row dependency wait timed out";
+    if (err & 4u) return "deblocking row wait timed out";
+    return "unknown";
+}
+
+// recon: the reconstruction kernel; deblock: the deblocking kernel over d_yuv (in place); color: RGB into d_rgb.  A deblocked
+// batch converts to RGB in the separate colour kernel: the reconstruction kernel's fused epilogue would see unfiltered samples.
+static int launch_all(mvhp_ctx *c, const mvhp_stream_params_t *p, const void *d_packed, int n_frames,
+                      uint8_t *d_yuv, uint8_t *d_rgb, hipStream_t st, bool recon, bool color, bool deblock)
+{
+    const bool fuse = recon && c->fused_color && !deblock;
+    if (deblock && mvhp::deblock_lds_bytes((int)p->width_mbs, mvhp::deblock_waves(n_frames)) > c->max_lds) {
+        set_err("picture too wide for the deblocking line buffer (%u macroblocks)", p->width_mbs);
+        return MVHP_UNSUPPORTED;
+    }
     if (recon) {
         mvhp::ReconArgs a;
         a.packed = (const uint8_t *)d_packed;
         a.yuv = d_yuv;
-        a.rgb = (c->fused_color && color) ? d_rgb : nullptr;
+        a.rgb = (fuse && color) ? d_rgb : nullptr;
         a.err = c->d_err;
         a.width_mbs = (int)p->width_mbs;
         a.height_mbs = (int)p->height_mbs;
@@ -457,7 +473,19 @@ static int launch_all(mvhp_ctx *c, const mvhp_stream_params_t *p, const void *d_
             HIP_TRY(mvhp::launch_recon(a, n_frames, nw, st));
         }
     }
-    if (color && d_rgb && !(recon && c->fused_color)) {
+    if (deblock) {
+        mvhp::DeblockArgs da;
+        da.packed = (const uint8_t *)d_packed;
+        da.yuv = d_yuv;
+        da.err = c->d_err;
+        da.width_mbs = (int)p->width_mbs;
+        da.height_mbs = (int)p->height_mbs;
+        da.n_frames = n_frames;
+        da.cqp_off_cb = p->chroma_qp_index_offset;
+        da.cqp_off_cr = p->second_chroma_qp_index_offset;
+        HIP_TRY(mvhp::launch_deblock(da, mvhp::deblock_waves(n_frames), st));
+    }
+    if (color && d_rgb && !fuse) {
         mvhp::ColorArgs ca;
         ca.yuv = d_yuv;
         ca.rgb = d_rgb;
@@ -478,7 +506,7 @@ MVHP_EXPORT int mvhp_recon_batch_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *
     }
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    return launch_all(c, p, d_packed, n_frames, d_yuv, d_rgb, st, true, true);
+    return launch_all(c, p, d_packed, n_frames, d_yuv, d_rgb, st, true, true, (p->flags & MVHP_PARAM_DEBLOCK) != 0);
 }
 
 MVHP_EXPORT int mvhp_expand_compact_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p, const void *d_compact, size_t stride,
@@ -503,13 +531,15 @@ MVHP_EXPORT int mvhp_expand_compact_dev(mvhp_ctx_t *c, const mvhp_stream_params_
 MVHP_EXPORT int mvhp_recon_stages_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p, const void *d_packed,
                                       int n_frames, uint8_t *d_yuv, uint8_t *d_rgb, void *stream, int stages)
 {
-    if (!c || !params_ok(p) || !d_packed || !d_yuv || n_frames <= 0 || (stages & ~3) || !stages) {
+    if (!c || !params_ok(p) || !d_packed || !d_yuv || n_frames <= 0 || (stages & ~7) || !stages) {
         set_err("mvhp_recon_stages_dev: invalid argument");
         return MVHP_FAILURE;
     }
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    return launch_all(c, p, d_packed, n_frames, d_yuv, d_rgb, st, (stages & 1) != 0, (stages & 2) != 0);
+    const bool recon = (stages & MVHP_STAGE_RECON) != 0;
+    return launch_all(c, p, d_packed, n_frames, d_yuv, d_rgb, st, recon, (stages & MVHP_STAGE_COLOR) != 0,
+                      (stages & MVHP_STAGE_DEBLOCK) || (recon && (p->flags & MVHP_PARAM_DEBLOCK)));
 }
 
 static int ensure(void **ptr, size_t *have, size_t need)
@@ -539,7 +569,8 @@ MVHP_EXPORT int mvhp_recon_batch_host(mvhp_ctx_t *c, const mvhp_stream_params_t 
     if (h_rgb && ensure((void **)&c->d_rgb, &c->d_rgb_bytes, rb) != MVHP_SUCCESS) return MVHP_FAILURE;
     HIP_TRY(hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_packed, h_packed, pb, hipMemcpyHostToDevice, c->stream));
-    int rc = launch_all(c, p, c->d_packed, n_frames, c->d_yuv, h_rgb ? c->d_rgb : nullptr, c->stream, true, true);
+    int rc = launch_all(c, p, c->d_packed, n_frames, c->d_yuv, h_rgb ? c->d_rgb : nullptr, c->stream, true, true,
+                        (p->flags & MVHP_PARAM_DEBLOCK) != 0);
     if (rc != MVHP_SUCCESS) return rc;
     HIP_TRY(hipMemcpyAsync(h_yuv, c->d_yuv, yb, hipMemcpyDeviceToHost, c->stream));
     if (h_rgb) HIP_TRY(hipMemcpyAsync(h_rgb, c->d_rgb, rb, hipMemcpyDeviceToHost, c->stream));
@@ -547,8 +578,7 @@ MVHP_EXPORT int mvhp_recon_batch_host(mvhp_ctx_t *c, const mvhp_stream_params_t 
     HIP_TRY(hipMemcpyAsync(&err, c->d_err, sizeof(err), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (err) {
-        set_err("reconstruction kernel reported error word 0x%x (%s)", err,
-                (err & 2u) ? "a workgroup's ticket lay outside the launch" : "row dependency wait timed out");
+        set_err("reconstruction kernel reported error word 0x%x (%s)", err, err_word_text(err));
         return MVHP_FAILURE;
     }
     return MVHP_SUCCESS;
@@ -563,8 +593,7 @@ MVHP_EXPORT int mvhp_sync_check(mvhp_ctx_t *c, void *stream)
     HIP_TRY(hipMemcpyAsync(&err, c->d_err, sizeof(err), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (err) {
-        set_err("reconstruction kernel reported error word 0x%x (%s)", err,
-                (err & 2u) ? "a workgroup's ticket lay outside the launch" : "row dependency wait timed out");
+        set_err("reconstruction kernel reported error word 0x%x (%s)", err, err_word_text(err));
         hipMemset(c->d_err, 0, sizeof(uint32_t));
         return MVHP_FAILURE;
     }
@@ -717,7 +746,7 @@ int eng_recon(DevCtx *d, const mvhp_stream_params_t *p, const void *d_compact, s
     ENG_TRY(hipSetDevice(c->device));
     ENG_TRY(hipEventRecord(d->ev[2], c->stream));
     if (mvhp_expand_compact_dev(c, p, d_compact, stride, n, d_packed, c->stream) != MVHP_SUCCESS) { err = mvhp_last_error(); return MVHP_FAILURE; }
-    const int rc = launch_all(c, p, d_packed, n, d_yuv, d_rgb, c->stream, true, true);
+    const int rc = launch_all(c, p, d_packed, n, d_yuv, d_rgb, c->stream, true, true, (p->flags & MVHP_PARAM_DEBLOCK) != 0);
     if (rc != MVHP_SUCCESS) { err = mvhp_last_error(); return rc; }
     ENG_TRY(hipEventRecord(d->ev[3], c->stream));
     uint32_t ew = 0;
@@ -729,7 +758,7 @@ int eng_recon(DevCtx *d, const mvhp_stream_params_t *p, const void *d_compact, s
     if (waves) *waves = c->last_waves;
     if (ew) {
         (void)hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), c->stream);
-        err = "reconstruction kernel reported error word (row dependency wait timed out)";
+        err = std::string("reconstruction kernel reported error word (") + err_word_text(ew) + ")";
         return MVHP_FAILURE;
     }
     return MVHP_SUCCESS;

@@ -74,4 +74,16 @@ hipError_t launch_recon_oct(const ReconArgs &a, int nw, hipStream_t stream);
 hipError_t launch_color(const ColorArgs &a, hipStream_t stream);
 hipError_t launch_expand(const ExpandArgs &a, hipStream_t stream);
 
+// the deblocking filter (deblock.hip): in place on the planes, one workgroup of `nw` (4 or 16) wavefronts per picture
+struct DeblockArgs {
+    const uint8_t *packed;   // the pictures' packed records (headers only are read)
+    uint8_t       *yuv;      // n_frames reconstructed pictures, filtered in place
+    uint32_t      *err;      // device word: bit 2 = row wait timed out
+    int            width_mbs, height_mbs, n_frames;
+    int            cqp_off_cb, cqp_off_cr;
+};
+size_t     deblock_lds_bytes(int width_mbs, int nw);
+int        deblock_waves(int n_frames);
+hipError_t launch_deblock(const DeblockArgs &a, int nw, hipStream_t stream);
+
 } // namespace mvhp

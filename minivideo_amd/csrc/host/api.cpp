@@ -517,6 +517,8 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     s.size = buf.size();
     // opt-in: index and reconstruct by the standard instead of by the reference's quirks
     if (const char *e = getenv("MINIVIDEO_SPEC")) s.spec = atoi(e) != 0;
+    // opt-in, independent of the above: the in-loop deblocking filter (clause 8.7), which the reference does not apply
+    if (const char *e = getenv("MINIVIDEO_DEBLOCK")) s.deblock = atoi(e) != 0;
     std::string err;
     const int brc = (m->container == CONTAINER_MP4) ? s.build_mp4(err) : s.build(err);
     if (brc != h264::RC_SUCCESS) { log_err("%s", err.c_str()); return FAILURE; }

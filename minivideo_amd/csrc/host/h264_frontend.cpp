@@ -333,8 +333,8 @@ int parse_pps(BitReader &br, const Sps *sps_table, Pps &p, std::string &err, boo
 // ---------------------------------------------------------------------------
 // picture decoder
 // ---------------------------------------------------------------------------
-PictureDecoder::PictureDecoder(const Sps &sps, const Pps &pps, int nal_ref_idc, bool spec)
-    : sps_(sps), pps_(pps), nal_ref_idc_(nal_ref_idc), W_(sps.width_mbs), H_(sps.height_map_units), spec_(spec)
+PictureDecoder::PictureDecoder(const Sps &sps, const Pps &pps, int nal_ref_idc, bool spec, bool deblock)
+    : sps_(sps), pps_(pps), nal_ref_idc_(nal_ref_idc), W_(sps.width_mbs), H_(sps.height_map_units), spec_(spec), deblock_(deblock)
 {
 }
 
@@ -434,11 +434,23 @@ int PictureDecoder::slice_header(std::string &err)
     slice_qp_ = 26 + pps_.pic_init_qp_minus26 + slice_qp_delta; // :293
     qp_prev_ = slice_qp_;
     if (slice_qp_ < 0 || slice_qp_ > 51) { err = "slice: SliceQPY out of range"; return RC_FAILURE; }
+    unsigned idc = 0;                          // (absent: 0, and both offsets 0 -- 7.4.3)
+    int alpha_div2 = 0, beta_div2 = 0;
     if (pps_.deblocking_filter_control_present) {
-        const unsigned idc = br_.ue();         // parsed and ignored: the reference never deblocks
-        if (idc != 1) { br_.se(); br_.se(); }
+        idc = br_.ue();                        // the reference never deblocks: kept only for MVHP_STREAM_DEBLOCK streams
+        if (idc != 1) { alpha_div2 = br_.se(); beta_div2 = br_.se(); }
     }
     if (br_.overrun()) { err = "slice header truncated"; return RC_FAILURE; }
+    dbk_flags_ = dbk_offsets_ = 0;
+    if (deblock_) {
+        if (idc > 2) { err = "slice: disable_deblocking_filter_idc out of range"; return RC_FAILURE; }
+        if (alpha_div2 < -6 || alpha_div2 > 6 || beta_div2 < -6 || beta_div2 > 6) {
+            err = "slice: deblocking filter offsets out of range (-6..6)";
+            return RC_FAILURE;
+        }
+        dbk_flags_ = (uint8_t)(idc << MVHP_DBK_IDC_SHIFT);
+        dbk_offsets_ = (uint8_t)((alpha_div2 & 15) | ((beta_div2 & 15) << 4));
+    }
     return RC_SUCCESS;
 }
 
@@ -603,6 +615,8 @@ int PictureDecoder::pcm_samples(int addr, std::string &err)
     h.mb_kind = MVHP_KIND_IPCM;
     h.qp_y = (uint8_t)qp_prev_;
     h.unavail = unavail_bits(addr);
+    h.flags = dbk_flags_;
+    h.dbk_offsets = dbk_offsets_;
     if (!compact_) {
         uint8_t *rec = out_ + (size_t)addr * MVHP_MB_BYTES;
         memcpy(rec, &h, sizeof(h));
@@ -611,7 +625,7 @@ int PictureDecoder::pcm_samples(int addr, std::string &err)
     }
     uint8_t *rec = cw_;   // compact record in its dense form (flags bit 0): header + the 768-byte area
     mb_off_[addr] = (uint32_t)(rec - cw_base_);
-    h.flags = 1;
+    h.flags |= 1;
     memcpy(rec, &h, sizeof(h));
     memcpy(rec + MVHP_MB_HEADER_BYTES, area, sizeof(area));
     cw_ = rec + MVHP_MB_HEADER_BYTES + sizeof(area);
@@ -701,6 +715,8 @@ int PictureDecoder::macroblock(int addr, std::string &err)
     h.chroma_pred_mode = mb.chroma_pred_mode;
     h.i16_pred_mode = (uint8_t)i16_mode;
     h.unavail = unavail_bits(addr);
+    h.flags = dbk_flags_;
+    h.dbk_offsets = dbk_offsets_;
     memcpy(h.pred_mode, mb.pred, 16);
     uint32_t nz = nz_cur_;   // collected while the blocks were decoded: every decoded level is non-zero
     if (mb.kind == MVHP_KIND_I8x8)
@@ -722,7 +738,7 @@ int PictureDecoder::macroblock(int addr, std::string &err)
         memset(dense, 0, sizeof(dense));
         for (uint32_t i = 0; i < n; i++) dense[ent[i] & 0xffffu] = (int16_t)(ent[i] >> 16);
         memcpy(ent, dense, sizeof(dense));
-        h.flags = 1;
+        h.flags |= 1;
         h.reserved1 = 0;
         cw_ = rec + MVHP_MB_HEADER_BYTES + sizeof(dense);
     } else {

@@ -121,7 +121,9 @@ class PictureDecoder {
 public:
     // spec = MVHP_STREAM_SPEC: the standard's slice semantics (first_mb_in_slice honoured, a slice ends where its data ends,
     // I_PCM accepted); otherwise the reference's (one slice NAL = one picture decoded from macroblock 0, h264_slice.c:1019)
-    PictureDecoder(const Sps &sps, const Pps &pps, int nal_ref_idc, bool spec = false);
+    // deblock = MVHP_STREAM_DEBLOCK: the records carry each slice's disable_deblocking_filter_idc and filter offsets
+    // (mvhp_mb_header_t::flags bits 1-2, dbk_offsets); otherwise the slice header's deblocking syntax is parsed and dropped
+    PictureDecoder(const Sps &sps, const Pps &pps, int nal_ref_idc, bool spec = false, bool deblock = false);
     ~PictureDecoder();
     // rbsp: slice NAL payload (after the NAL header byte), emulation prevention removed.
     int decode(const uint8_t *rbsp, size_t n, uint8_t *packed, size_t packed_bytes, std::string &err);
@@ -189,6 +191,9 @@ private:
     int  pcm_samples(int addr, std::string &err);
     uint8_t unavail_bits(int addr) const;
     bool       spec_ = false;
+    bool       deblock_ = false;
+    uint8_t    dbk_flags_ = 0;       // header.flags bits 1-2 / header.dbk_offsets of the slice being parsed (deblock_ only)
+    uint8_t    dbk_offsets_ = 0;
     int        slice_first_ = 0;     // address of the first macroblock of the slice being parsed
     int        next_addr_ = 0;       // macroblocks decoded so far (= the address the next slice must start at)
     bool       multi_slice_ = false; // records carry MVHP_UNAVAIL_* bits

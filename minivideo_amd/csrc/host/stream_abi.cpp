@@ -170,7 +170,7 @@ int mvhp_stream::decode_packed(int k, void *packed, size_t bytes, std::string &e
     std::vector<std::vector<uint8_t>> store;
     std::vector<SliceRbsp> slices;
     picture_slices(*this, idr, store, slices);
-    PictureDecoder pd(idr.sps, idr.pps, slices[0].nal_ref_idc, spec);
+    PictureDecoder pd(idr.sps, idr.pps, slices[0].nal_ref_idc, spec, deblock);
     return pd.decode_slices(slices.data(), (int)slices.size(), (uint8_t *)packed, bytes, err);
 }
 
@@ -183,7 +183,7 @@ int mvhp_stream::decode_compact(int k, void *buf, size_t cap, size_t *used, std:
     std::vector<std::vector<uint8_t>> store;
     std::vector<SliceRbsp> slices;
     picture_slices(*this, idr, store, slices);
-    PictureDecoder pd(idr.sps, idr.pps, slices[0].nal_ref_idc, spec);
+    PictureDecoder pd(idr.sps, idr.pps, slices[0].nal_ref_idc, spec, deblock);
     return pd.decode_slices_compact(slices.data(), (int)slices.size(), (uint8_t *)buf, cap, used, err);
 }
 
@@ -207,12 +207,13 @@ MVHP_EXPORT int mvhp_stream_open(const uint8_t *data, size_t size, mvhp_stream_t
 
 MVHP_EXPORT int mvhp_stream_open_ex(const uint8_t *data, size_t size, uint32_t flags, mvhp_stream_t **out)
 {
-    if (!out || !data || (flags & ~MVHP_STREAM_SPEC)) return MVHP_FAILURE;
+    if (!out || !data || (flags & ~(MVHP_STREAM_SPEC | MVHP_STREAM_DEBLOCK))) return MVHP_FAILURE;
     *out = nullptr;
     mvhp_stream *s = new mvhp_stream();
     s->data = data;
     s->size = size;
     s->spec = (flags & MVHP_STREAM_SPEC) != 0;
+    s->deblock = (flags & MVHP_STREAM_DEBLOCK) != 0;
     if (s->build(g_stream_err) != RC_SUCCESS) { delete s; return MVHP_FAILURE; }
     *out = s;
     return MVHP_SUCCESS;
@@ -242,7 +243,8 @@ MVHP_EXPORT int mvhp_stream_params(const mvhp_stream_t *s, int idr, mvhp_stream_
     out->height_mbs = (uint32_t)i.sps.height_map_units;
     out->chroma_qp_index_offset = i.pps.chroma_qp_index_offset;
     out->second_chroma_qp_index_offset = i.pps.second_chroma_qp_index_offset;
-    out->flags = (i.pps.transform_8x8_mode ? MVHP_PARAM_MAY_HAVE_8X8 : 0u) | (s->spec ? MVHP_PARAM_SPEC_LUMA_DC : 0u);
+    out->flags = (i.pps.transform_8x8_mode ? MVHP_PARAM_MAY_HAVE_8X8 : 0u) | (s->spec ? MVHP_PARAM_SPEC_LUMA_DC : 0u) |
+                 (s->deblock ? MVHP_PARAM_DEBLOCK : 0u);
     memset(out->scaling4, 16, sizeof(out->scaling4));
     memset(out->scaling8, 16, sizeof(out->scaling8));
     if (s->spec) {   // SURVEY 8f row f4 (outside parity): several slices, scaling matrices

@@ -34,6 +34,9 @@ def lib():
         L.mvgen_stream_ex.restype = C.c_size_t
         L.mvgen_stream_ex.argtypes = [C.POINTER(GenCfg), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
                                       C.c_void_p]
+        L.mvgen_stream_dbk.restype = C.c_size_t
+        L.mvgen_stream_dbk.argtypes = [C.POINTER(GenCfg), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -59,10 +62,15 @@ def make_stream(width_mbs, height_mbs, n_frames, seed=1, profile="baseline", den
 
 
 def make_stream_ex(width_mbs, height_mbs, n_frames, seed=1, profile="baseline", slices=1, pcm_permille=0, scaling=0, dense=True,
-                   cqp_offsets=(0, 0), sps_pps_every_frame=False, qp_range=(24, 32), max_level=32, allow_qp36_i16=True):
+                   cqp_offsets=(0, 0), sps_pps_every_frame=False, qp_range=(24, 32), max_level=32, allow_qp36_i16=True, deblock=None):
     """Streams OUTSIDE the reference's envelope (what MVHP_STREAM_SPEC decodes by the standard): `slices` slices
     per picture, pcm_permille / 1000 of the macroblocks I_PCM, scaling lists in the SPS (scaling & 1) and / or the PPS (scaling & 2;
-    'high*' profiles only).  Returns (stream, packed[n, W*H, 800], weights[112] = scaling4[3][16] | scaling8[64] in raster order)."""
+    'high*' profiles only).  Returns (stream, packed[n, W*H, 800], weights[112] = scaling4[3][16] | scaling8[64] in raster order).
+
+    deblock: None (no deblocking syntax: the PPS leaves deblocking_filter_control_present_flag 0, the stream is byte-identical to
+    the one without the argument) or e.g. dict(idc=(0, 1, 2), offsets=(-6, 6)): every slice draws disable_deblocking_filter_idc
+    from `idc` and both offsets (div2) from the closed range `offsets`; the records carry them (mvhp_mb_header_t::flags bits 1-2,
+    dbk_offsets).  The macroblocks are those of the same call without `deblock`."""
     prof = {"baseline": (66, 0, 0), "main": (77, 1, 0), "main_cavlc": (77, 0, 0), "high": (100, 1, 1),
             "high_cavlc": (100, 0, 1), "high_4x4": (100, 1, 0)}[profile]
     cfg = GenCfg(width_mbs, height_mbs, n_frames, seed, prof[0], prof[1], prof[2], 1 if dense else 0,
@@ -71,10 +79,20 @@ def make_stream_ex(width_mbs, height_mbs, n_frames, seed=1, profile="baseline", 
     L = lib()
     packed = np.zeros((n_frames, width_mbs * height_mbs, 800), np.uint8)
     weights = np.zeros(112, np.uint8)
-    n = L.mvgen_stream_ex(C.byref(cfg), slices, pcm_permille, scaling, None, 0, packed.ctypes.data, weights.ctypes.data)
+    if deblock is None:
+        def call(out, cap):
+            return L.mvgen_stream_ex(C.byref(cfg), slices, pcm_permille, scaling, out, cap, packed.ctypes.data, weights.ctypes.data)
+    else:
+        mask = sum(1 << int(k) for k in deblock.get("idc", (0,)))
+        lo, hi = deblock.get("offsets", (0, 0))
+
+        def call(out, cap):
+            return L.mvgen_stream_dbk(C.byref(cfg), slices, pcm_permille, scaling, mask, lo, hi, out, cap, packed.ctypes.data,
+                                      weights.ctypes.data)
+    n = call(None, 0)
     if n == 0:
         raise ValueError("generator rejected the configuration")
     out = np.zeros(n, np.uint8)
-    n2 = L.mvgen_stream_ex(C.byref(cfg), slices, pcm_permille, scaling, out.ctypes.data, n, packed.ctypes.data, weights.ctypes.data)
+    n2 = call(out.ctypes.data, n)
     assert n2 == n
     return out, packed, weights

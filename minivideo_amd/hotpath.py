@@ -5,6 +5,9 @@ import os
 import numpy as np
 
 SUCCESS, FAILURE, UNSUPPORTED = 1, 0, -1
+STREAM_SPEC, STREAM_DEBLOCK = 1, 2                                     # mvhp_stream_open_ex flags (MVHP_STREAM_*)
+PARAM_MAY_HAVE_8X8, PARAM_SPEC_LUMA_DC, PARAM_SLICES, PARAM_SCALING, PARAM_DEBLOCK = 1, 2, 4, 8, 16   # MVHP_PARAM_*
+STAGE_RECON, STAGE_COLOR, STAGE_DEBLOCK = 1, 2, 4                      # mvhp_recon_stages_dev (MVHP_STAGE_*)
 MB_BYTES = 800
 MB_HEADER_BYTES = 32
 
