@@ -242,6 +242,49 @@ MVHP_EXPORT int  mvhp_recon_stages_dev(mvhp_ctx_t *ctx, const mvhp_stream_params
                                        const void *d_packed, int n_frames,
                                        uint8_t *d_yuv, uint8_t *d_rgb, void *stream, int stages);
 
+/* ---------------------------------------------------------------------------
+ * Output geometry: device-buffer building blocks for callers that want the visible or a downscaled picture.  Only callers
+ * of these entry points get it: the decode engine, minivideo_decode and the CLIs always deliver the coded size, as the
+ * reference does, which parses the SPS crop (h264_parameterset.c:360-378) and never applies it.
+ *   crop: the SPS frame-cropping rectangle (7.4.2.1.1; 4:2:0 frames: CropUnitX = CropUnitY = 2), luma samples:
+ *         x = 2 left, y = 2 top, w = 16 W - 2 (left + right), h = 16 H - 2 (top + bottom); chroma is the same rectangle halved.
+ *   box:  the cropped picture fitted into box_w x box_h (DESIGN.md 3 "Output geometry": aspect kept, even sides, never
+ *         enlarged) by an integer area-average filter that is exact for D = S (crop only is the same pass).
+ * Thumbnails assume square samples (VUI sample aspect ratio is not parsed).
+ * ------------------------------------------------------------------------- */
+typedef struct mvhp_output_geometry {
+    uint32_t crop_x, crop_y, crop_w, crop_h;   /* luma rectangle of the coded picture that is kept (all even)          */
+    uint32_t out_w, out_h;                     /* size of the output picture (even; equal to crop_w / crop_h, or less) */
+    uint32_t reserved[2];
+} mvhp_output_geometry_t;
+
+#define MVHP_OUTPUT_CROP 1u   /* mvhp_output_request_t::flags: pictures are the SPS's cropped rectangle         */
+#define MVHP_OUTPUT_BOX  2u   /* ... fitted into box_w x box_h (implies MVHP_OUTPUT_CROP); box sides >= 2     */
+typedef struct mvhp_output_request {
+    uint32_t flags;           /* MVHP_OUTPUT_*; 0 = the coded size (what the reference writes)                  */
+    uint32_t box_w, box_h;
+    uint32_t reserved;
+} mvhp_output_request_t;
+
+/* The SPS cropping rectangle of IDR picture `idr` (out_w / out_h = its size; a stream without frame_cropping_flag gives
+ * the coded size).  Information only: it changes nothing.  MVHP_FAILURE (mvhp_stream_last_error() says why) when the
+ * picture has no parameter sets or the crop leaves nothing (w <= 0 or h <= 0). */
+MVHP_EXPORT int    mvhp_stream_crop(const mvhp_stream_t *s, int idr, mvhp_output_geometry_t *out);
+/* The output geometry of picture `idr` under `req` (NULL or flags 0: the coded size, no crop). */
+MVHP_EXPORT int    mvhp_output_geometry(const mvhp_stream_t *s, int idr, const mvhp_output_request_t *req,
+                                        mvhp_output_geometry_t *out);
+/* The size rule alone: cw x ch (even) fitted into bw x bh (each >= 2) -> *ow x *oh. */
+MVHP_EXPORT int    mvhp_geometry_fit(uint32_t cw, uint32_t ch, uint32_t bw, uint32_t bh, uint32_t *ow, uint32_t *oh);
+/* Bytes of one output picture: planar Y | Cb | Cr of out_w x out_h, and interleaved RGB8. */
+MVHP_EXPORT size_t mvhp_geometry_yuv_bytes(const mvhp_output_geometry_t *g);
+MVHP_EXPORT size_t mvhp_geometry_rgb_bytes(const mvhp_output_geometry_t *g);
+/* n coded pictures (d_yuv_coded: n * mvhp_yuv_frame_bytes(p), 16-byte aligned) -> n output pictures of geometry g: planes
+ * into d_yuv_out (n * mvhp_geometry_yuv_bytes(g), may be NULL) and / or RGB (the reference's integer formula, 2x2-nearest
+ * chroma) into d_rgb_out (n * mvhp_geometry_rgb_bytes(g), may be NULL); both 4-byte aligned.  Asynchronous on `stream`
+ * (NULL = the context's own). */
+MVHP_EXPORT int    mvhp_resample_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                                     const uint8_t *d_yuv_coded, int n, uint8_t *d_yuv_out, uint8_t *d_rgb_out, void *stream);
+
 /* Page-locked host memory for the host-buffer entry points (H2D / D2H at full PCIe rate). */
 MVHP_EXPORT void *mvhp_host_alloc(size_t bytes);
 MVHP_EXPORT void  mvhp_host_free(void *p);

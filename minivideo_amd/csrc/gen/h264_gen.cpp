@@ -206,6 +206,9 @@ struct GenCfg {
     int deblock = 0;
     int dbk_idc_mask = 1;        // bit k: disable_deblocking_filter_idc k may be drawn for a slice
     int dbk_off_min = 0, dbk_off_max = 0;   // slice_alpha_c0_offset_div2 / slice_beta_offset_div2 range
+    // frame cropping (mvgen_stream_crop; 0 = frame_cropping_flag 0, as every other stream)
+    int n_crops = 0;
+    const int32_t *crops = nullptr;         // n_crops x {left, right, top, bottom}
 };
 
 struct MbSyntax {
@@ -237,6 +240,7 @@ struct Gen {
     // configuration without it
     Rng dbk_rng;
     uint8_t dbk_flags = 0, dbk_offsets = 0;   // record fields of the slice being written
+    int sps_written = 0;
 
     // ---- random syntax ----
     void rand_block(int *lev, int n, double p_coded, double geo, int first = 0)
@@ -907,7 +911,14 @@ struct Gen {
         bw.ue((uint32_t)H - 1);
         bw.bit(1);               // frame_mbs_only_flag
         bw.bit(1);               // direct_8x8_inference_flag
-        bw.bit(0);               // frame_cropping_flag
+        if (cfg.n_crops > 0) {   // mvgen_stream_crop: SPS k carries crop k % n_crops
+            const int32_t *c = cfg.crops + 4 * (sps_written % cfg.n_crops);
+            bw.bit(1);           // frame_cropping_flag
+            for (int i = 0; i < 4; i++) bw.ue((uint32_t)c[i]);   // left, right, top, bottom offsets
+        } else {
+            bw.bit(0);           // frame_cropping_flag
+        }
+        sps_written++;
         bw.bit(0);               // vui_parameters_present_flag
         bw.trailing();
         emit_nal(out, 3, 7, bw.bytes);
@@ -1090,6 +1101,25 @@ size_t mvgen_stream_dbk(const mvgen_cfg_t *c, int32_t n_slices, int32_t pcm_perm
     g.dbk_off_min = off_min;
     g.dbk_off_max = off_max;
     return run_generator(g, out, cap, packed, weights);
+}
+
+// mvgen_stream plus SPS frame cropping: SPS number k of the stream (one per picture with sps_pps_every_frame) writes
+// frame_cropping_flag = 1 and the offsets crops[4 * (k % n_crops) ..] = {left, right, top, bottom}.  The macroblocks and records
+// are those of mvgen_stream with the same configuration.
+__attribute__((visibility("default")))
+size_t mvgen_stream_crop(const mvgen_cfg_t *c, int32_t n_crops, const int32_t *crops, uint8_t *out, size_t cap, uint8_t *packed)
+{
+    if (!c || c->width_mbs <= 0 || c->height_mbs <= 0 || c->n_frames <= 0) return 0;
+    if (c->profile_idc != 66 && c->profile_idc != 77 && c->profile_idc != 100) return 0;
+    if (c->cabac && c->profile_idc == 66) return 0;
+    if (c->transform8x8 && c->profile_idc != 100) return 0;
+    if (n_crops < 1 || !crops) return 0;
+    for (int i = 0; i < 4 * n_crops; i++)
+        if (crops[i] < 0) return 0;
+    GenCfg g = to_cfg(c);
+    g.n_crops = n_crops;
+    g.crops = crops;
+    return run_generator(g, out, cap, packed, nullptr);
 }
 
 } // extern "C"

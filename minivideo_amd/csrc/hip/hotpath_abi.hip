@@ -542,6 +542,46 @@ MVHP_EXPORT int mvhp_recon_stages_dev(mvhp_ctx_t *c, const mvhp_stream_params_t 
                       (stages & MVHP_STAGE_DEBLOCK) || (recon && (p->flags & MVHP_PARAM_DEBLOCK)));
 }
 
+MVHP_EXPORT int mvhp_resample_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                                  const uint8_t *d_yuv_coded, int n, uint8_t *d_yuv_out, uint8_t *d_rgb_out, void *stream)
+{
+    if (!c || !params_ok(p) || !g || !d_yuv_coded || n <= 0 || ((uintptr_t)d_yuv_coded & 15) || ((uintptr_t)d_yuv_out & 3) ||
+        ((uintptr_t)d_rgb_out & 3)) {
+        set_err("mvhp_resample_dev: invalid argument");
+        return MVHP_FAILURE;
+    }
+    const uint32_t Wp = p->width_mbs * 16, Hp = p->height_mbs * 16;
+    const bool even = ((g->crop_x | g->crop_y | g->crop_w | g->crop_h | g->out_w | g->out_h) & 1u) == 0;
+    if (!even || g->crop_w < 2 || g->crop_h < 2 || g->crop_x > Wp || g->crop_w > Wp - g->crop_x || g->crop_y > Hp ||
+        g->crop_h > Hp - g->crop_y || g->out_w < 2 || g->out_h < 2 || g->out_w > g->crop_w || g->out_h > g->crop_h) {
+        set_err("mvhp_resample_dev: geometry outside the coded picture (crop %u,%u %ux%u -> %ux%u of %ux%u)", g->crop_x,
+                g->crop_y, g->crop_w, g->crop_h, g->out_w, g->out_h, Wp, Hp);
+        return MVHP_FAILURE;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    mvhp::ResampleArgs a;
+    a.src = d_yuv_coded;
+    a.yuv = d_yuv_out;
+    a.rgb = d_rgb_out;
+    a.width_mbs = (int)p->width_mbs;
+    a.height_mbs = (int)p->height_mbs;
+    a.n_frames = n;
+    a.cx = (int)g->crop_x; a.cy = (int)g->crop_y; a.cw = (int)g->crop_w; a.ch = (int)g->crop_h;
+    a.ow = (int)g->out_w; a.oh = (int)g->out_h;
+    // chroma output rows per workgroup: four (eight luma rows), fewer when that would leave CUs idle or not fit the LDS
+    int band = 4;
+    while (band > 1 && (double)n * ((a.oh / 2 + band - 1) / band) < 4.0 * c->n_cus) band /= 2;
+    while (band > 1 && mvhp::resample_lds_bytes(a.cw, a.ow, band) > c->max_lds) band /= 2;
+    if (mvhp::resample_lds_bytes(a.cw, a.ow, band) > c->max_lds) {
+        set_err("mvhp_resample_dev: picture too wide for the LDS row buffers (%u samples)", g->crop_w);
+        return MVHP_UNSUPPORTED;
+    }
+    a.band = band;
+    if (!d_yuv_out && !d_rgb_out) return MVHP_SUCCESS;
+    HIP_TRY(mvhp::launch_resample(a, stream ? (hipStream_t)stream : c->stream));
+    return MVHP_SUCCESS;
+}
+
 static int ensure(void **ptr, size_t *have, size_t need)
 {
     if (*have >= need) return MVHP_SUCCESS;

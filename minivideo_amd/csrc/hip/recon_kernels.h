@@ -86,4 +86,18 @@ size_t     deblock_lds_bytes(int width_mbs, int nw);
 int        deblock_waves(int n_frames);
 hipError_t launch_deblock(const DeblockArgs &a, int nw, hipStream_t stream);
 
+// the output-geometry pass (resample.hip): coded planes -> cropped / resampled planes and / or RGB, one workgroup per
+// (picture, band of `band` chroma output rows = 2 * band luma rows)
+struct ResampleArgs {
+    const uint8_t *src;      // n_frames coded pictures, planar Y | Cb | Cr, 16-byte aligned
+    uint8_t       *yuv;      // n_frames output pictures (ow x oh planes) or NULL
+    uint8_t       *rgb;      // n_frames output RGB pictures or NULL
+    int            width_mbs, height_mbs, n_frames;
+    int            cx, cy, cw, ch;   // luma crop rectangle (even)
+    int            ow, oh;           // output size (even, <= cw / ch)
+    int            band;             // chroma output rows per workgroup
+};
+size_t     resample_lds_bytes(int cw, int ow, int band);
+hipError_t launch_resample(const ResampleArgs &a, hipStream_t stream);
+
 } // namespace mvhp

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "../hip/resample_taps.h"
 #include "h264_frontend.h"
 #include "mp4_demux.h"
 #include "stream_internal.h"
@@ -254,6 +255,74 @@ MVHP_EXPORT int mvhp_stream_params(const mvhp_stream_t *s, int idr, mvhp_stream_
             out->flags |= MVHP_PARAM_SCALING;
     }
     return MVHP_SUCCESS;
+}
+
+// The SPS cropping rectangle (7.4.2.1.1; frame macroblocks, 4:2:0: CropUnitX = CropUnitY = 2).  The reference derives the
+// same (h264_parameterset.c:360-378) and never applies it; nothing here changes what a picture decodes to.
+MVHP_EXPORT int mvhp_stream_crop(const mvhp_stream_t *s, int idr, mvhp_output_geometry_t *out)
+{
+    if (!s || !out || idr < 0 || (size_t)idr >= s->idrs.size() || !s->idrs[idr].ok) {
+        g_stream_err = "mvhp_stream_crop: no parameter sets for this picture";
+        return MVHP_FAILURE;
+    }
+    const Sps &sps = s->idrs[idr].sps;
+    const int64_t W = (int64_t)sps.width_mbs * 16, H = (int64_t)sps.height_map_units * 16;
+    int64_t c[4] = {0, 0, 0, 0};   // left, right, top, bottom (frame_crop_*_offset)
+    if (sps.frame_cropping)
+        for (int i = 0; i < 4; i++) c[i] = (int64_t)(uint32_t)sps.crop[i];
+    const int64_t w = W - 2 * (c[0] + c[1]), h = H - 2 * (c[2] + c[3]);
+    if (w <= 0 || h <= 0) {
+        g_stream_err = "SPS frame cropping leaves no picture (" + std::to_string(W) + "x" + std::to_string(H) + " coded, offsets " +
+                       std::to_string(c[0]) + " " + std::to_string(c[1]) + " " + std::to_string(c[2]) + " " + std::to_string(c[3]) + ")";
+        return MVHP_FAILURE;
+    }
+    memset(out, 0, sizeof(*out));
+    out->crop_x = (uint32_t)(2 * c[0]);
+    out->crop_y = (uint32_t)(2 * c[2]);
+    out->crop_w = out->out_w = (uint32_t)w;
+    out->crop_h = out->out_h = (uint32_t)h;
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT int mvhp_geometry_fit(uint32_t cw, uint32_t ch, uint32_t bw, uint32_t bh, uint32_t *ow, uint32_t *oh)
+{
+    uint32_t w = 0, h = 0;
+    if (!ow || !oh || (cw & 1) || (ch & 1) || !mvrs::fit(cw, ch, bw, bh, w, h)) return MVHP_FAILURE;
+    *ow = w;
+    *oh = h;
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT int mvhp_output_geometry(const mvhp_stream_t *s, int idr, const mvhp_output_request_t *req, mvhp_output_geometry_t *out)
+{
+    if (!req || req->flags == 0) {   // the coded size
+        mvhp_stream_params_t p;
+        if (!out || mvhp_stream_params(s, idr, &p) != MVHP_SUCCESS) {
+            g_stream_err = "mvhp_output_geometry: no parameter sets for this picture";
+            return MVHP_FAILURE;
+        }
+        memset(out, 0, sizeof(*out));
+        out->crop_w = out->out_w = p.width_mbs * 16;
+        out->crop_h = out->out_h = p.height_mbs * 16;
+        return MVHP_SUCCESS;
+    }
+    if ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX)) || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2))) {
+        g_stream_err = "mvhp_output_geometry: malformed request (box sides must be at least 2)";
+        return MVHP_FAILURE;
+    }
+    if (mvhp_stream_crop(s, idr, out) != MVHP_SUCCESS) return MVHP_FAILURE;
+    if (req->flags & MVHP_OUTPUT_BOX) mvrs::fit(out->crop_w, out->crop_h, req->box_w, req->box_h, out->out_w, out->out_h);
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT size_t mvhp_geometry_yuv_bytes(const mvhp_output_geometry_t *g)
+{
+    return g ? (size_t)g->out_w * g->out_h * 3 / 2 : 0;
+}
+
+MVHP_EXPORT size_t mvhp_geometry_rgb_bytes(const mvhp_output_geometry_t *g)
+{
+    return g ? (size_t)g->out_w * g->out_h * 3 : 0;
 }
 
 MVHP_EXPORT int mvhp_stream_decode_packed(const mvhp_stream_t *s, int idr, void *packed, size_t packed_bytes)

@@ -37,8 +37,31 @@ def lib():
         L.mvgen_stream_dbk.restype = C.c_size_t
         L.mvgen_stream_dbk.argtypes = [C.POINTER(GenCfg), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.mvgen_stream_crop.restype = C.c_size_t
+        L.mvgen_stream_crop.argtypes = [C.POINTER(GenCfg), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         _LIB = L
     return _LIB
+
+
+def make_stream_crop(width_mbs, height_mbs, n_frames, crops, seed=1, profile="baseline", dense=True, cqp_offsets=(0, 0),
+                     sps_pps_every_frame=False, qp_range=(24, 32), max_level=32, allow_qp36_i16=False):
+    """make_stream with SPS frame cropping: `crops` is a list of (left, right, top, bottom) offsets; SPS k of the stream (one
+    per picture with sps_pps_every_frame) carries crops[k % len(crops)].  The macroblocks are those of make_stream with the same
+    arguments.  Returns (stream, packed[n, W*H, 800])."""
+    prof = {"baseline": (66, 0, 0), "main": (77, 1, 0), "main_cavlc": (77, 0, 0), "high": (100, 1, 1),
+            "high_cavlc": (100, 0, 1), "high_4x4": (100, 1, 0)}[profile]
+    cfg = GenCfg(width_mbs, height_mbs, n_frames, seed, prof[0], prof[1], prof[2], 1 if dense else 0,
+                 cqp_offsets[0], cqp_offsets[1], int(sps_pps_every_frame), int(allow_qp36_i16),
+                 qp_range[0], qp_range[1], max_level)
+    L = lib()
+    cr = np.ascontiguousarray(np.array(crops, np.int32).reshape(-1, 4))
+    packed = np.zeros((n_frames, width_mbs * height_mbs, 800), np.uint8)
+    n = L.mvgen_stream_crop(C.byref(cfg), cr.shape[0], cr.ctypes.data, None, 0, packed.ctypes.data)
+    if n == 0:
+        raise ValueError("generator rejected the configuration")
+    out = np.zeros(n, np.uint8)
+    assert L.mvgen_stream_crop(C.byref(cfg), cr.shape[0], cr.ctypes.data, out.ctypes.data, n, packed.ctypes.data) == n
+    return out, packed
 
 
 def make_stream(width_mbs, height_mbs, n_frames, seed=1, profile="baseline", dense=True, cqp_offsets=(0, 0),

@@ -51,6 +51,68 @@ class StreamParams(C.Structure):
         return self.mbs * 768
 
 
+OUTPUT_CROP, OUTPUT_BOX = 1, 2                                          # mvhp_output_request_t flags (MVHP_OUTPUT_*)
+
+
+class OutputGeometry(C.Structure):
+    """mvhp_output_geometry_t: the luma crop rectangle of the coded picture and the output size"""
+    _fields_ = [("crop_x", C.c_uint32), ("crop_y", C.c_uint32), ("crop_w", C.c_uint32), ("crop_h", C.c_uint32),
+                ("out_w", C.c_uint32), ("out_h", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    @property
+    def yuv_bytes(self):
+        return int(self.out_w) * int(self.out_h) * 3 // 2
+
+    @property
+    def rgb_bytes(self):
+        return int(self.out_w) * int(self.out_h) * 3
+
+
+class OutputRequest(C.Structure):
+    """mvhp_output_request_t"""
+    _fields_ = [("flags", C.c_uint32), ("box_w", C.c_uint32), ("box_h", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def output_request(output):
+    """None -> None (the coded size); "crop" -> the SPS crop; (w, h) -> the crop fitted into a w x h box"""
+    if output is None:
+        return None
+    if output == "crop":
+        return OutputRequest(OUTPUT_CROP, 0, 0, 0)
+    w, h = output
+    return OutputRequest(OUTPUT_CROP | OUTPUT_BOX, int(w), int(h), 0)
+
+
+def geometry(crop_x, crop_y, crop_w, crop_h, out_w=None, out_h=None):
+    g = OutputGeometry()
+    g.crop_x, g.crop_y, g.crop_w, g.crop_h = crop_x, crop_y, crop_w, crop_h
+    g.out_w, g.out_h = crop_w if out_w is None else out_w, crop_h if out_h is None else out_h
+    return g
+
+
+def geometry_fit(cw, ch, bw, bh):
+    """the size rule (mvhp_geometry_fit): (out_w, out_h), or None for malformed arguments"""
+    L = lib()
+    ow, oh = C.c_uint32(), C.c_uint32()
+    if L.mvhp_geometry_fit(cw, ch, bw, bh, C.byref(ow), C.byref(oh)) != SUCCESS:
+        return None
+    return ow.value, oh.value
+
+
+def stream_crop(stream_handle, idr):
+    """mvhp_stream_crop: OutputGeometry of the SPS crop of picture `idr`, or None (mvhp_stream_last_error() says why)"""
+    g = OutputGeometry()
+    return g if lib().mvhp_stream_crop(stream_handle, int(idr), C.byref(g)) == SUCCESS else None
+
+
+def output_geometry(stream_handle, idr, output):
+    """mvhp_output_geometry under output_request(output), or None"""
+    g = OutputGeometry()
+    req = output_request(output)
+    rc = lib().mvhp_output_geometry(stream_handle, int(idr), C.byref(req) if req is not None else None, C.byref(g))
+    return g if rc == SUCCESS else None
+
+
 def lib_path():
     # MINIVIDEO_LIB: developer override used for A/B experiments with alternative builds of the same library
     return os.environ.get("MINIVIDEO_LIB") or os.path.join(_HERE, "libminivideo.so")
@@ -96,6 +158,19 @@ def lib():
     L.mvhp_sync_check.argtypes = [vp, vp]
     L.mvhp_last_launch_info.restype = i32
     L.mvhp_last_launch_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    pg, u32 = C.POINTER(OutputGeometry), C.c_uint32
+    L.mvhp_stream_crop.restype = i32
+    L.mvhp_stream_crop.argtypes = [vp, i32, pg]
+    L.mvhp_output_geometry.restype = i32
+    L.mvhp_output_geometry.argtypes = [vp, i32, C.POINTER(OutputRequest), pg]
+    L.mvhp_geometry_fit.restype = i32
+    L.mvhp_geometry_fit.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
+    for f in ("mvhp_geometry_yuv_bytes", "mvhp_geometry_rgb_bytes"):
+        getattr(L, f).restype = sz
+        getattr(L, f).argtypes = [pg]
+    L.mvhp_resample_dev.restype = i32
+    L.mvhp_resample_dev.argtypes = [vp, pp, pg, vp, i32, vp, vp, vp]
+    L.mvhp_stream_last_error.restype = C.c_char_p
     if hasattr(L, "mvhp_stream_open"):
         L.mvhp_stream_open.restype = i32
         L.mvhp_stream_open.argtypes = [vp, sz, C.POINTER(vp)]
@@ -184,6 +259,12 @@ class HotPath:
                                            stream, int(stages))
         if rc != SUCCESS:
             raise _err(self._L, "mvhp_recon_stages_dev")
+
+    def resample_dev(self, params, geom, d_yuv_coded, n, d_yuv_out=None, d_rgb_out=None, stream=None):
+        """n coded pictures (device) -> n pictures of OutputGeometry `geom`: planes and / or RGB (device)"""
+        rc = self._L.mvhp_resample_dev(self._h, C.byref(params), C.byref(geom), d_yuv_coded, int(n), d_yuv_out, d_rgb_out, stream)
+        if rc != SUCCESS:
+            raise _err(self._L, "mvhp_resample_dev")
 
     def sync_check(self, stream=None):
         if self._L.mvhp_sync_check(self._h, stream) != SUCCESS:
