@@ -15,6 +15,13 @@
  *   - no deblocking filter is applied by default; the picture is the uncropped coded size
  *     (opt-in, outside the reference's behaviour: MINIVIDEO_DEBLOCK=1 in the environment applies the standard's in-loop
  *     deblocking filter, clause 8.7, to Annex-B and MP4 input alike; independent of MINIVIDEO_SPEC=1);
+ *   - opt-in, outside the reference's behaviour and independent of the two switches above: MINIVIDEO_CROP=1 writes the SPS's
+ *     cropped rectangle instead of the coded size (1920x1080 instead of 1920x1088), MINIVIDEO_THUMBNAIL=<w>x<h> writes the
+ *     cropped picture fitted into a w x h box (aspect kept, even sides, never enlarged; it implies the crop; both sides 2 ...
+ *     65535), made on the GPU.  Every format is written at that size, file names do not change, Annex-B and MP4 input behave
+ *     alike.  A malformed MINIVIDEO_THUMBNAIL ("abc", "0x10", "320", a side below 2) is not ignored: minivideo_decode()
+ *     returns FAILURE with a message before any device work.  A picture whose crop leaves nothing is skipped like a picture
+ *     that does not decode;
  *   - H.264 IDR pictures only, from Annex-B elementary streams (.264/.h264 or a
  *     file starting with an SPS start code) or from the first H.264 video track
  *     of an MP4/MOV file (demuxer/mp4/mp4.c:1950 mp4_fileParse -> sync samples).

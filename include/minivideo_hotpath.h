@@ -243,9 +243,11 @@ MVHP_EXPORT int  mvhp_recon_stages_dev(mvhp_ctx_t *ctx, const mvhp_stream_params
                                        uint8_t *d_yuv, uint8_t *d_rgb, void *stream, int stages);
 
 /* ---------------------------------------------------------------------------
- * Output geometry: device-buffer building blocks for callers that want the visible or a downscaled picture.  Only callers
- * of these entry points get it: the decode engine, minivideo_decode and the CLIs always deliver the coded size, as the
- * reference does, which parses the SPS crop (h264_parameterset.c:360-378) and never applies it.
+ * Output geometry (opt-in): the visible or a downscaled picture instead of the coded size.  By default every entry point
+ * delivers the coded size, as the reference does, which parses the SPS crop (h264_parameterset.c:360-378) and never applies
+ * it.  An mvhp_output_request_t asks for more: mvhp_engine_decode_ex takes one, minivideo_decode builds one from
+ * MINIVIDEO_CROP / MINIVIDEO_THUMBNAIL (include/minivideo.h), and the functions below are the pieces for callers that manage
+ * device buffers themselves.
  *   crop: the SPS frame-cropping rectangle (7.4.2.1.1; 4:2:0 frames: CropUnitX = CropUnitY = 2), luma samples:
  *         x = 2 left, y = 2 top, w = 16 W - 2 (left + right), h = 16 H - 2 (top + bottom); chroma is the same rectangle halved.
  *   box:  the cropped picture fitted into box_w x box_h (DESIGN.md 3 "Output geometry": aspect kept, even sides, never
@@ -308,6 +310,11 @@ MVHP_EXPORT int  mvhp_last_launch_info(const mvhp_ctx_t *ctx, int *layout, int *
 /* 1 (default): the reconstruction kernel converts to RGB in its epilogue when d_rgb is given;
  * 0: a separate colour kernel reads the planes back.  Speed only, never results. */
 MVHP_EXPORT int  mvhp_set_fused_color(mvhp_ctx_t *ctx, int on);
+
+/* 1 (default): mvhp_resample_dev runs geometries with out_w == crop_w and out_h == crop_h (crop only) on the copy kernel
+ * (global memory to global memory, no LDS row buffers: their width limit does not apply); 0: on the general resample kernel,
+ * for which such a geometry is one tap of 2^14 per axis, i.e. the same bytes.  Speed only, never results. */
+MVHP_EXPORT int  mvhp_set_crop_copy(mvhp_ctx_t *ctx, int on);
 
 /* Tuning knob (speed only, never results): waves per picture workgroup
  * (4, 6, 8, 12 or 16; a layout that is not built for the value takes the next smaller one);
@@ -384,7 +391,8 @@ typedef struct mvhp_decode_stats {
     double   first_picture_s;      /* from the call to the first picture at the sink                                 */
     uint64_t host_alloc_bytes, dev_alloc_bytes;
     uint32_t placed_buffers;       /* 1: the device batch buffers come from mvhp_placed_alloc (MINIVIDEO_PLACED=1)   */
-    uint32_t reserved;
+    uint32_t geometry_launches;    /* launches that ran the output-geometry pass behind the reconstruction (mvhp_engine_decode_ex
+                                      with a request that changes the picture); 0 on the coded-size path                      */
     uint32_t launches_wide[4];     /* launches on MVHP_LAYOUT_WIDE, _QUAD_WIDE, _PIPE, _PIPE1 (launches_by_layout: 0..3)   */
 } mvhp_decode_stats_t;
 
@@ -409,6 +417,20 @@ MVHP_EXPORT void mvhp_engine_destroy(mvhp_engine_t *e);
  * were accepted, or when the list ended after at least one. */
 MVHP_EXPORT int  mvhp_engine_decode(mvhp_engine_t *e, const mvhp_stream_t *s, const int *order, int n_order, int wanted,
                                     int want_rgb, mvhp_picture_sink_t sink, void *user, mvhp_decode_stats_t *stats);
+/* The same with an output request (see "Output geometry" above; NULL or flags 0 = the coded size) and a sink that also gets
+ * the picture's geometry: yuv holds mvhp_geometry_yuv_bytes(g), rgb mvhp_geometry_rgb_bytes(g).  mvhp_engine_decode is this
+ * call with req = NULL.  A batch holds pictures of one set of stream parameters and ONE geometry: a stream whose SPS crop
+ * changes from picture to picture is decoded in small batches.  Where the geometry of a picture equals the coded size (no
+ * SPS crop, no box or a box that already contains the picture) the engine takes the path of mvhp_engine_decode exactly;
+ * otherwise the batch is reconstructed without the fused colour epilogue, deblocked when the stream asks for it, passed
+ * through mvhp_resample_dev on the device, and only the output pictures are downloaded (stats: geometry_launches).  A picture
+ * whose geometry cannot be formed (the SPS crop leaves nothing) reaches the sink as a failed picture (g all zero, err says
+ * why); decoding goes on. */
+typedef int (*mvhp_picture_sink_ex_t)(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *p,
+                                      const mvhp_output_geometry_t *g, const uint8_t *yuv, const uint8_t *rgb);
+MVHP_EXPORT int  mvhp_engine_decode_ex(mvhp_engine_t *e, const mvhp_stream_t *s, const int *order, int n_order, int wanted,
+                                       int want_rgb, const mvhp_output_request_t *req, mvhp_picture_sink_ex_t sink, void *user,
+                                       mvhp_decode_stats_t *stats);
 /* Gives back a picture the sink kept (verdict 2) during the running mvhp_engine_decode call; anything else is ignored. */
 MVHP_EXPORT void mvhp_engine_release_picture(mvhp_engine_t *e, int seq);
 

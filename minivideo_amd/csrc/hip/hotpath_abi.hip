@@ -56,6 +56,7 @@ struct mvhp_ctx {
     int          waves;       // 0 = auto
     int          layout;      // MVHP_LAYOUT_*
     int          fused_color; // 1 = RGB written by the reconstruction kernel's epilogue (default)
+    int          crop_copy;   // 1 = crop-only geometries run the copy kernel (crop_copy.hip), 0 = the general resample kernel
     int          n_cus;
     size_t       max_lds;
     int          last_layout, last_waves;   // what the last reconstruction launch used
@@ -122,6 +123,7 @@ MVHP_EXPORT int mvhp_create(int device, mvhp_ctx_t **out)
     memset(c, 0, sizeof(*c));
     c->device = device;
     c->fused_color = 1;
+    c->crop_copy = 1;
     if (const char *e = getenv("MINIVIDEO_LAYOUT")) { // tuning / test override, speed only
         if (!strcmp(e, "rows")) c->layout = MVHP_LAYOUT_ROWS;
         else if (!strcmp(e, "quad")) c->layout = MVHP_LAYOUT_QUAD;
@@ -194,6 +196,13 @@ MVHP_EXPORT int mvhp_set_fused_color(mvhp_ctx_t *c, int on)
 {
     if (!c) return MVHP_FAILURE;
     c->fused_color = on ? 1 : 0;
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT int mvhp_set_crop_copy(mvhp_ctx_t *c, int on)
+{
+    if (!c) return MVHP_FAILURE;
+    c->crop_copy = on ? 1 : 0;
     return MVHP_SUCCESS;
 }
 
@@ -568,6 +577,16 @@ MVHP_EXPORT int mvhp_resample_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p, 
     a.n_frames = n;
     a.cx = (int)g->crop_x; a.cy = (int)g->crop_y; a.cw = (int)g->crop_w; a.ch = (int)g->crop_h;
     a.ow = (int)g->out_w; a.oh = (int)g->out_h;
+    if (c->crop_copy && a.ow == a.cw && a.oh == a.ch) {   // crop only: a copy (the same bytes; no LDS row buffers, so any width)
+        if (!d_yuv_out && !d_rgb_out) return MVHP_SUCCESS;
+        // chroma rows per workgroup: eight (sixteen luma rows: about eight 16-byte blocks per lane at 1080p), fewer when the
+        // grid would leave CUs idle
+        int band = 8;
+        while (band > 1 && (double)n * ((a.ch / 2 + band - 1) / band) < 4.0 * c->n_cus) band /= 2;
+        a.band = band;
+        HIP_TRY(mvhp::launch_crop_copy(a, stream ? (hipStream_t)stream : c->stream));
+        return MVHP_SUCCESS;
+    }
     // chroma output rows per workgroup: four (eight luma rows), fewer when that would leave CUs idle or not fit the LDS
     int band = 4;
     while (band > 1 && (double)n * ((a.oh / 2 + band - 1) / band) < 4.0 * c->n_cus) band /= 2;
@@ -778,16 +797,25 @@ int eng_d2h(DevCtx *d, int n, void *const *dst, const void *const *src, const si
     return MVHP_SUCCESS;
 }
 
-int eng_recon(DevCtx *d, const mvhp_stream_params_t *p, const void *d_compact, size_t stride, void *d_packed, int n, uint8_t *d_yuv,
-              uint8_t *d_rgb, float *ms, int *layout, int *waves, std::string &err)
+// g == NULL: planes (+ RGB into d_rgb) of the coded size.  Otherwise: planes of the coded size into d_yuv without the fused
+// colour epilogue, the deblocking filter when p asks for it, then the output-geometry pass into out_yuv / out_rgb.
+int eng_recon_impl(DevCtx *d, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const void *d_compact, size_t stride,
+                   void *d_packed, int n, uint8_t *d_yuv, uint8_t *d_rgb, uint8_t *out_yuv, uint8_t *out_rgb, float *ms, int *layout,
+                   int *waves, std::string &err)
 {
     mvhp_ctx *c = d->c;
     if (!params_ok(p) || !d_compact || !d_packed || !d_yuv || n <= 0) { err = "reconstruction: invalid argument"; return MVHP_FAILURE; }
     ENG_TRY(hipSetDevice(c->device));
     ENG_TRY(hipEventRecord(d->ev[2], c->stream));
     if (mvhp_expand_compact_dev(c, p, d_compact, stride, n, d_packed, c->stream) != MVHP_SUCCESS) { err = mvhp_last_error(); return MVHP_FAILURE; }
-    const int rc = launch_all(c, p, d_packed, n, d_yuv, d_rgb, c->stream, true, true, (p->flags & MVHP_PARAM_DEBLOCK) != 0);
+    const bool deblock = (p->flags & MVHP_PARAM_DEBLOCK) != 0;
+    int rc = g ? launch_all(c, p, d_packed, n, d_yuv, nullptr, c->stream, true, false, deblock)
+               : launch_all(c, p, d_packed, n, d_yuv, d_rgb, c->stream, true, true, deblock);
     if (rc != MVHP_SUCCESS) { err = mvhp_last_error(); return rc; }
+    if (g) {
+        rc = mvhp_resample_dev(c, p, g, d_yuv, n, out_yuv, out_rgb, c->stream);
+        if (rc != MVHP_SUCCESS) { err = mvhp_last_error(); return rc; }
+    }
     ENG_TRY(hipEventRecord(d->ev[3], c->stream));
     uint32_t ew = 0;
     ENG_TRY(hipEventSynchronize(d->ev[3]));   // (sleeps: blocking-sync event)
@@ -802,6 +830,20 @@ int eng_recon(DevCtx *d, const mvhp_stream_params_t *p, const void *d_compact, s
         return MVHP_FAILURE;
     }
     return MVHP_SUCCESS;
+}
+
+int eng_recon(DevCtx *d, const mvhp_stream_params_t *p, const void *d_compact, size_t stride, void *d_packed, int n, uint8_t *d_yuv,
+              uint8_t *d_rgb, float *ms, int *layout, int *waves, std::string &err)
+{
+    return eng_recon_impl(d, p, nullptr, d_compact, stride, d_packed, n, d_yuv, d_rgb, nullptr, nullptr, ms, layout, waves, err);
+}
+
+int eng_recon_geometry(DevCtx *d, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const void *d_compact, size_t stride,
+                       void *d_packed, int n, uint8_t *d_yuv_coded, uint8_t *d_yuv_out, uint8_t *d_rgb_out, float *ms, int *layout,
+                       int *waves, std::string &err)
+{
+    if (!g) { err = "reconstruction: no output geometry"; return MVHP_FAILURE; }
+    return eng_recon_impl(d, p, g, d_compact, stride, d_packed, n, d_yuv_coded, nullptr, d_yuv_out, d_rgb_out, ms, layout, waves, err);
 }
 
 // the engine's batch buffers from one placed arena (MINIVIDEO_PLACED=1): records / planes / RGB of a batch in three groups of
@@ -840,7 +882,7 @@ void eng_placed_free(DevCtx *d, void *arena)
 
 const mvengine::DeviceApi g_hip_api = {
     mvhp_device_count, mvhp_host_alloc, mvhp_host_free, eng_ctx_create, eng_ctx_destroy, eng_dev_alloc, eng_dev_free,
-    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_recon, eng_placed_alloc, eng_placed_free,
+    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_recon, eng_placed_alloc, eng_placed_free, eng_recon_geometry,
 };
 
 } // namespace

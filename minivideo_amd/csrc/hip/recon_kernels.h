@@ -99,5 +99,7 @@ struct ResampleArgs {
 };
 size_t     resample_lds_bytes(int cw, int ow, int band);
 hipError_t launch_resample(const ResampleArgs &a, hipStream_t stream);
+// crop only (ow == cw, oh == ch) as a copy from global memory to global memory (crop_copy.hip): the same bytes, no LDS, any width
+hipError_t launch_crop_copy(const ResampleArgs &a, hipStream_t stream);
 
 } // namespace mvhp

@@ -249,6 +249,35 @@ std::vector<int> select_idrs(const mvhp_stream &s, int picture_number, int mode)
     return sel;
 }
 
+// ---- MINIVIDEO_CROP=1 / MINIVIDEO_THUMBNAIL=<w>x<h> (opt-in, include/minivideo.h): the output request of the decode call.
+// A box implies the crop.  false: a malformed value (the call fails before any device work; it is not ignored).
+bool output_request_from_env(mvhp_output_request_t &req, std::string &why)
+{
+    memset(&req, 0, sizeof(req));
+    if (const char *e = getenv("MINIVIDEO_CROP"))
+        if (atoi(e) != 0) req.flags |= MVHP_OUTPUT_CROP;
+    const char *t = getenv("MINIVIDEO_THUMBNAIL");
+    if (!t || !*t) return true;
+    // decimal digits, 'x', decimal digits, nothing else; each side 2 ... 65535
+    unsigned long side[2] = {0, 0};
+    const char *q = t;
+    bool ok = true;
+    for (int k = 0; k < 2 && ok; k++) {
+        int digits = 0;
+        for (; *q >= '0' && *q <= '9' && digits < 6; q++, digits++) side[k] = side[k] * 10 + (unsigned long)(*q - '0');
+        ok = digits > 0 && side[k] >= 2 && side[k] <= 65535 && *q == (k == 0 ? 'x' : '\0');
+        if (k == 0) q++;
+    }
+    if (!ok) {
+        why = std::string("MINIVIDEO_THUMBNAIL='") + t + "' is not <width>x<height> with both sides between 2 and 65535";
+        return false;
+    }
+    req.flags |= MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX;
+    req.box_w = (uint32_t)side[0];
+    req.box_h = (uint32_t)side[1];
+    return true;
+}
+
 // ---- the sink of minivideo_decode: export.c:618-767 (file naming, format fallbacks, writers) ----
 // The pipeline itself (entropy threads -> H2D -> batched kernels -> D2H, frame-level work queue over every HIP
 // device) is the decode engine, csrc/host/decode_engine.cpp; it calls this once per picture, in stream order.
@@ -324,9 +353,10 @@ struct ExportSink {
         }
     }
 
-    static int call(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *p, const uint8_t *yuv,
-                    const uint8_t *rgb)
+    static int call(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *p,
+                    const mvhp_output_geometry_t *g, const uint8_t *yuv, const uint8_t *rgb)
     {
+        (void)p;
         ExportSink &x = *static_cast<ExportSink *>(user);
         if (rc != MVHP_SUCCESS) {
             log_err("IDR %d: %s", idr, err ? err : "failed");
@@ -339,7 +369,7 @@ struct ExportSink {
         if (x.picture_number > 1) name += "_" + std::to_string(x.exported);
         name += ".";
         name += x.ext;
-        const int W = (int)p->width_mbs * 16, H = (int)p->height_mbs * 16;
+        const int W = (int)g->out_w, H = (int)g->out_h;   // the coded size unless MINIVIDEO_CROP / MINIVIDEO_THUMBNAIL ask for less
         if (!x.pool.empty()) {
             // Writers run behind the pipeline, so a write that fails is only known later: no further picture is decoded in
             // its place (the synchronous path below does that).  Once one has failed -- a full disk does not get better --
@@ -484,6 +514,11 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     BitstreamMap_t *map = m->tracks_video[0];
     if (!map || map->stream_type != stream_VIDEO) { log_err("No video track to decode"); return FAILURE; }
     if (map->stream_codec != CODEC_H264) { log_err("Unable to decode given file format: no decoder available!"); return FAILURE; }
+    mvhp_output_request_t req;
+    {   // before any device work: a malformed switch fails the call
+        std::string why;
+        if (!output_request_from_env(req, why)) { log_err("%s", why.c_str()); return FAILURE; }
+    }
 
     // The engine (HIP runtime, one context per device, its thread pools: 0.2-0.5 s in a fresh process) comes up on a thread
     // of its own while this one reads and indexes the file.
@@ -566,7 +601,8 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     mvhp_decode_stats_t st;
     // decodes in order until `wanted` pictures have been written (h264.c:173-179) or 64 errors in a row (h264.c:181-187)
     // RGB formats are written from the RGB picture alone: the planes stay on the device
-    (void)mvhp_engine_decode(eng, &s, order.data(), (int)order.size(), wanted, want_rgb ? MVHP_OUT_RGB_ONLY : 0, ExportSink::call, &sink, &st);
+    (void)mvhp_engine_decode_ex(eng, &s, order.data(), (int)order.size(), wanted, want_rgb ? MVHP_OUT_RGB_ONLY : 0,
+                                req.flags ? &req : nullptr, ExportSink::call, &sink, &st);
     sink.finish();   // (every kept picture is back: mvhp_engine_decode waits for that)
     if (getenv("MINIVIDEO_STATS")) {
         fprintf(stderr, "[minivideo] decode call: reading the file %.3f s, indexing %.3f s, engine up after %.3f s (its thread took "
@@ -575,10 +611,10 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
         fprintf(stderr, "[minivideo] decode: %u pictures entropy-decoded, %u written, %u failed, %u launches (largest %u pictures), "
                         "%u contexts, %u host threads, %.3f s (first picture after %.3f s; page-locking %.3f s for %.2f GB, device "
                         "allocations %.3f s for %.2f GB, first launches %.3f s; entropy threads busy %.3f s, H2D %.3f s, kernels %.3f s, "
-                        "D2H %.3f s, sink %.3f s)\n", st.pictures_issued, st.pictures_ok, st.pictures_failed, st.batches,
+                        "D2H %.3f s for %.3f GB, sink %.3f s; %u launches with the output-geometry pass)\n", st.pictures_issued, st.pictures_ok, st.pictures_failed, st.batches,
                 st.max_batch_pictures, st.contexts, st.host_threads, st.wall_s, st.first_picture_s, st.host_alloc_s,
                 st.host_alloc_bytes / 1e9, st.dev_alloc_s, st.dev_alloc_bytes / 1e9, st.first_launch_s, st.entropy_busy_s, st.h2d_s,
-                st.kernel_s, st.d2h_s, st.sink_s);
+                st.kernel_s, st.d2h_s, st.d2h_bytes / 1e9, st.sink_s, st.geometry_launches);
     }
     if (sink.aborted) return FAILURE;
     if (sink.write_errors.load() > 0 && sink.written.load() < wanted) return FAILURE;   // files are missing because writes failed

@@ -3,7 +3,8 @@
 // Threads of one decode call (all joined before it returns):
 //   feeder              hands out pictures in `order`, never more than `wanted` minus what is already accepted or in
 //                       flight (the reference stops after picture_number IDRs, h264.c:173-179), grouped into chunks
-//                       (one H2D transfer) and batches (one kernel launch, one set of stream parameters);
+//                       (one H2D transfer) and batches (one kernel launch, one set of stream parameters, one output
+//                       geometry);
 //   T entropy workers   mvhp_stream::decode_compact() straight into a page-locked chunk slot (the compact transfer
 //                       format: only non-zero levels cross PCIe; the GPU expands it into packed records);
 //   per context:        uploader (claims whole batches from the shared queue: pictures are independent, so this is
@@ -80,6 +81,21 @@ bool same_params(const mvhp_stream_params_t &a, const mvhp_stream_params_t &b)
             (memcmp(a.scaling4, b.scaling4, sizeof(a.scaling4)) == 0 && memcmp(a.scaling8, b.scaling8, sizeof(a.scaling8)) == 0));
 }
 
+bool same_geometry(const mvhp_output_geometry_t &a, const mvhp_output_geometry_t &b)
+{
+    return a.crop_x == b.crop_x && a.crop_y == b.crop_y && a.crop_w == b.crop_w && a.crop_h == b.crop_h && a.out_w == b.out_w &&
+           a.out_h == b.out_h;
+}
+
+// the geometry of a picture delivered at its coded size
+mvhp_output_geometry_t coded_geometry(const mvhp_stream_params_t &p)
+{
+    mvhp_output_geometry_t g{};
+    g.crop_w = g.out_w = p.width_mbs * 16;
+    g.crop_h = g.out_h = p.height_mbs * 16;
+    return g;
+}
+
 struct Pinned {
     uint8_t *p = nullptr;
     size_t cap = 0;
@@ -105,6 +121,7 @@ struct PicResult {
     int rc = MVHP_FAILURE;
     std::string err;
     mvhp_stream_params_t params{};
+    mvhp_output_geometry_t geom{};   // what yuv / rgb hold (the coded size unless the call has an output request)
     OutChunk *oc = nullptr;
     const uint8_t *yuv = nullptr, *rgb = nullptr;
     bool ready = false;      // final: the sink may take it
@@ -119,6 +136,17 @@ struct DevBuf {
     size_t compact_cap = 0, packed_cap = 0, yuv_cap = 0, rgb_cap = 0;
     bool busy = false;
     bool arena_piece = false;   // the four buffers are pieces of the context's placed arena: never freed one by one
+    // output pictures of a batch with a geometry (what is downloaded then; yuv above is the pass's input).  Ordinary
+    // allocations always, also beside a placed arena: they are the small side of such a batch.
+    uint8_t *out_yuv = nullptr, *out_rgb = nullptr;
+    size_t out_yuv_cap = 0, out_rgb_cap = 0;
+    void leave_arena()          // the four arena pieces are forgotten (they go with the arena); the output buffers stay
+    {
+        compact = packed = nullptr;
+        yuv = rgb = nullptr;
+        compact_cap = packed_cap = yuv_cap = rgb_cap = 0;
+        arena_piece = false;
+    }
 };
 
 // slot size of a compact picture: the format's upper bound, 16-byte aligned
@@ -139,6 +167,8 @@ size_t write_empty_compact(uint8_t *buf, size_t mbs)
 struct Batch {
     int id = 0;
     mvhp_stream_params_t params{};
+    mvhp_output_geometry_t geom{};   // of every picture of the batch
+    bool use_geom = false;           // geom differs from the coded size: the batch runs the device table's recon_geometry
     std::vector<int> seqs;           // slot -> position in `order`
     int capacity = 0;                // planned pictures (device buffers are sized for it)
     int total = -1;                  // pictures, known once the closing chunk has been issued
@@ -193,8 +223,8 @@ public:
     Engine(const DeviceApi &api) : api_(api) {}
     ~Engine();
     bool init(const mvhp_engine_opts_t *opts, std::string &err);
-    int decode(const mvhp_stream &s, const int *order, int n_order, int wanted, int out_mask, mvhp_picture_sink_t sink,
-               void *user, mvhp_decode_stats_t *stats, std::string &err);
+    int decode(const mvhp_stream &s, const int *order, int n_order, int wanted, int out_mask, const mvhp_output_request_t *req,
+               mvhp_picture_sink_t sink, mvhp_picture_sink_ex_t sink_ex, void *user, mvhp_decode_stats_t *stats, std::string &err);
 
 private:
     // ---- threads ----
@@ -214,10 +244,12 @@ public:
     void release_picture(int seq);   // any thread
 private:
     bool grow(Pinned &p, size_t need);   // no lock needed
-    int batch_capacity(const mvhp_stream_params_t &p, int remaining) const;
+    int batch_capacity(const mvhp_stream_params_t &p, const mvhp_output_geometry_t *g, int remaining) const;
+    bool picture_geometry(int idr, const mvhp_stream_params_t &p, mvhp_output_geometry_t &g, bool &use, std::string &why) const;
     int planned_batch(int cap, int remaining, int batch_id) const;
     int chunk_pictures(const mvhp_stream_params_t &p) const;
     bool ensure_devbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err);   // no lock needed
+    bool ensure_outbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err);   // no lock needed
 
     const DeviceApi &api_;
     mvhp_engine_opts_t opts_{};
@@ -234,6 +266,7 @@ private:
     const int *order_ = nullptr;
     int n_order_ = 0, wanted_ = 0;
     bool want_rgb_ = false, want_yuv_ = true;   // which outputs are downloaded (the planes are always reconstructed)
+    mvhp_output_request_t req_{};               // flags 0: pictures of the coded size
     bool stop_ = false;
     bool sink_waiting_ = false;
     int pos_ = 0;                 // next position of `order` the feeder has not issued yet
@@ -267,7 +300,7 @@ Engine::~Engine()
     for (auto &c : all_out_) { api_.host_free(c->yuv.p); api_.host_free(c->rgb.p); }
     for (Ctx &c : ctx_) {
         if (c.arena) {   // pieces of the arena go with it; a buffer that left the arena is freed below like any other
-            for (DevBuf &b : c.bufs) if (b.arena_piece) b = DevBuf();
+            for (DevBuf &b : c.bufs) if (b.arena_piece) b.leave_arena();
             api_.placed_free(c.dev, c.arena);
         }
         for (DevBuf &b : c.bufs) {
@@ -275,6 +308,8 @@ Engine::~Engine()
             if (b.packed) api_.dev_free(c.dev, b.packed);
             if (b.yuv) api_.dev_free(c.dev, b.yuv);
             if (b.rgb) api_.dev_free(c.dev, b.rgb);
+            if (b.out_yuv) api_.dev_free(c.dev, b.out_yuv);
+            if (b.out_rgb) api_.dev_free(c.dev, b.out_rgb);
         }
         if (c.dev) api_.ctx_destroy(c.dev);
     }
@@ -352,7 +387,24 @@ int Engine::chunk_pictures(const mvhp_stream_params_t &p) const
 // for 2048 pictures on one context and 16 threads (round 2 started and ended on 64);
 // long jobs run most of their pictures in 1024-picture launches.  Modelled wall for 2048 x 1080p: 0.56 s against 0.63 s
 // with 1024 512 256 128 64 64 and 0.535 s of pure entropy work.
-int Engine::batch_capacity(const mvhp_stream_params_t &p, int remaining) const
+// The geometry of picture `idr` under the call's request.  use = it differs from the coded size (otherwise the picture takes
+// the path of a call without a request: fused RGB, no extra pass, no extra buffers).  false: it cannot be formed (`why`).
+bool Engine::picture_geometry(int idr, const mvhp_stream_params_t &p, mvhp_output_geometry_t &g, bool &use, std::string &why) const
+{
+    g = coded_geometry(p);
+    use = false;
+    if (req_.flags == 0) return true;
+    if (mvhp_output_geometry(s_, idr, &req_, &g) != MVHP_SUCCESS) {
+        const char *e = mvhp_stream_last_error();
+        why = (e && *e) ? e : "the output geometry cannot be formed";
+        g = mvhp_output_geometry_t{};
+        return false;
+    }
+    use = !same_geometry(g, coded_geometry(p));
+    return true;
+}
+
+int Engine::batch_capacity(const mvhp_stream_params_t &p, const mvhp_output_geometry_t *g, int remaining) const
 {
     const int n_ctx = (int)ctx_.size();
     // the cap: four pictures per CU (the four-picture kernel's full round); a long job -- from 4096 pictures per context on --
@@ -360,7 +412,8 @@ int Engine::batch_capacity(const mvhp_stream_params_t &p, int remaining) const
     // product path reaches the kernel the bench times; the ramp and the taper stay as they are)
     int cap = opts_.batch_pictures > 0 ? opts_.batch_pictures : ((n_order_ >= 4096 * n_ctx) ? 2048 : 1024);
     const size_t per_pic = compact_slot_bytes(p) + mvhp_packed_frame_bytes(&p) + mvhp_yuv_frame_bytes(&p) +
-                           (want_rgb_ ? mvhp_rgb_frame_bytes(&p) : 0);
+                           (g ? (want_yuv_ ? mvhp_geometry_yuv_bytes(g) : 0) + (want_rgb_ ? mvhp_geometry_rgb_bytes(g) : 0)
+                              : (want_rgb_ ? mvhp_rgb_frame_bytes(&p) : 0));
     size_t budget = ctx_[0].mem_budget;
     for (const Ctx &c : ctx_) budget = std::min(budget, c.mem_budget);
     const int mem_cap = (int)std::min<size_t>(1 << 20, std::max<size_t>(1, budget / std::max<size_t>(1, per_pic)));
@@ -441,12 +494,11 @@ bool Engine::ensure_devbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
         const size_t n = (size_t)bt.capacity;
         if (n * compact_slot_bytes(bt.params) <= b.compact_cap && n * mvhp_packed_frame_bytes(&bt.params) <= b.packed_cap &&
             n * mvhp_yuv_frame_bytes(&bt.params) <= b.yuv_cap && n * mvhp_rgb_frame_bytes(&bt.params) <= b.rgb_cap)
-            return true;
+            return ensure_outbuf(c, b, bt, err);
         // a batch the arena was not sized for (another picture size, a later and longer job): this batch buffer leaves the
         // arena for ordinary allocations -- its pieces stay where they are until the engine goes (batch_capacity() keeps
         // batches of the arena's own shape inside it)
-        b = DevBuf();
-        b.busy = true;
+        b.leave_arena();
     }
     auto need = [&](void **ptr, size_t *cap, size_t bytes) {
         if (*cap >= bytes) return true;
@@ -468,8 +520,35 @@ bool Engine::ensure_devbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
     if (!need(&b.compact, &b.compact_cap, n * compact_slot_bytes(bt.params)) ||
         !need(&b.packed, &b.packed_cap, n * mvhp_packed_frame_bytes(&bt.params)) ||
         !need((void **)&b.yuv, &b.yuv_cap, n * mvhp_yuv_frame_bytes(&bt.params)) ||
-        (want_rgb_ && !need((void **)&b.rgb, &b.rgb_cap, n * mvhp_rgb_frame_bytes(&bt.params)))) {
+        (want_rgb_ && !bt.use_geom && !need((void **)&b.rgb, &b.rgb_cap, n * mvhp_rgb_frame_bytes(&bt.params)))) {
         err = "out of device memory for a batch of " + std::to_string(bt.capacity) + " pictures";
+        return false;
+    }
+    return ensure_outbuf(c, b, bt, err);
+}
+
+// the output pictures of a batch with a geometry: n x mvhp_geometry_{yuv,rgb}_bytes, sized for the batch at hand (geometries
+// change inside a job; these buffers are the small side of a batch)
+bool Engine::ensure_outbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
+{
+    if (!bt.use_geom) return true;
+    const size_t n = (size_t)bt.capacity;
+    auto need = [&](uint8_t **ptr, size_t *cap, size_t bytes) {
+        if (*cap >= bytes) return true;
+        const double t0 = now_s();
+        if (*ptr) api_.dev_free(c.dev, *ptr);
+        *ptr = (uint8_t *)api_.dev_alloc(c.dev, bytes);
+        *cap = *ptr ? bytes : 0;
+        {
+            std::lock_guard<std::mutex> l(alloc_mu_);
+            alloc_dev_s_ += now_s() - t0;
+            alloc_dev_bytes_ += bytes;
+        }
+        return *ptr != nullptr;
+    };
+    if ((want_yuv_ && !need(&b.out_yuv, &b.out_yuv_cap, n * mvhp_geometry_yuv_bytes(&bt.geom))) ||
+        (want_rgb_ && !need(&b.out_rgb, &b.out_rgb_cap, n * mvhp_geometry_rgb_bytes(&bt.geom)))) {
+        err = "out of device memory for the output pictures of a batch of " + std::to_string(bt.capacity);
         return false;
     }
     return true;
@@ -523,8 +602,25 @@ void Engine::feeder()
             cv_.notify_all();
             continue;
         }
-        if (cur && !same_params(cur->params, p0)) {   // a batch holds one set of stream parameters
-            close_batch(cur);
+        mvhp_output_geometry_t g0{};
+        bool use0 = false;
+        {
+            std::string why;
+            if (!picture_geometry(order_[first_seq], p0, g0, use0, why)) {
+                // a picture whose geometry cannot be formed (the crop leaves nothing) fails without occupying a slot
+                PicResult &r = results_[(size_t)first_seq];
+                r.rc = MVHP_FAILURE;
+                r.err = why;
+                r.params = p0;
+                r.ready = true;
+                if (rg) { if (++rg->pos >= rg->seqs.size()) retry_q_.pop_front(); }
+                else { pos_++; issued_++; }
+                cv_.notify_all();
+                continue;
+            }
+        }
+        if (cur && (!same_params(cur->params, p0) || !same_geometry(cur->geom, g0))) {   // a batch holds one set of stream
+            close_batch(cur);                                                              // parameters and one geometry
             cur = nullptr;
         }
         const int avail = rg ? (int)(rg->seqs.size() - rg->pos) : std::min(allowance(), n_order_ - pos_);
@@ -532,7 +628,9 @@ void Engine::feeder()
             auto nb = std::make_unique<Batch>();
             nb->id = next_batch_id_++;
             nb->params = p0;
-            nb->capacity = batch_capacity(p0, avail);
+            nb->geom = g0;
+            nb->use_geom = use0;
+            nb->capacity = batch_capacity(p0, use0 ? &g0 : nullptr, avail);
             nb->retry = rg != nullptr;
             nb->exclude_ctx = rg ? rg->exclude_ctx : -1;
             nb->seqs.reserve((size_t)nb->capacity);
@@ -547,6 +645,10 @@ void Engine::feeder()
         while (same < n) {
             mvhp_stream_params_t pi{};
             if (mvhp_stream_params(s_, order_[seq_at(same)], &pi) != MVHP_SUCCESS || !same_params(pi, p0)) break;
+            mvhp_output_geometry_t gi{};
+            bool ui = false;
+            std::string why;
+            if (!picture_geometry(order_[seq_at(same)], pi, gi, ui, why) || !same_geometry(gi, g0)) break;
             same++;
         }
         n = same;
@@ -595,6 +697,7 @@ void Engine::feeder()
                 cur->seqs.push_back(seq);
                 PicResult &r = results_[(size_t)seq];
                 r.params = p0;
+                r.geom = g0;
                 r.parsed_ok = false;
                 work_q_.push_back(Item{c, i, seq});
             }
@@ -814,8 +917,14 @@ void Engine::launcher(int k)
         int rc = MVHP_SUCCESS;
         const double t_call = now_s();
         if (inject) { rc = MVHP_FAILURE; err = "injected failure (test hook)"; }
-        else rc = api_.recon(cx.dev, &b->params, b->buf->compact, compact_slot_bytes(b->params), b->buf->packed, b->total,
-                             b->buf->yuv, want_rgb_ ? b->buf->rgb : nullptr, &ms, &layout, &waves, err);
+        else if (!b->use_geom)
+            rc = api_.recon(cx.dev, &b->params, b->buf->compact, compact_slot_bytes(b->params), b->buf->packed, b->total,
+                            b->buf->yuv, want_rgb_ ? b->buf->rgb : nullptr, &ms, &layout, &waves, err);
+        else if (!api_.recon_geometry) { rc = MVHP_FAILURE; err = "this device table has no output-geometry operation"; }
+        else
+            rc = api_.recon_geometry(cx.dev, &b->params, &b->geom, b->buf->compact, compact_slot_bytes(b->params), b->buf->packed,
+                                     b->total, b->buf->yuv, want_yuv_ ? b->buf->out_yuv : nullptr,
+                                     want_rgb_ ? b->buf->out_rgb : nullptr, &ms, &layout, &waves, err);
         if (!cx.launched_once) {   // host time of the first call beyond the device time: code-object load, first-launch setup
             cx.launched_once = true;
             std::lock_guard<std::mutex> la(alloc_mu_);
@@ -825,6 +934,7 @@ void Engine::launcher(int k)
             std::lock_guard<std::mutex> l(mu_);
             if (rc == MVHP_SUCCESS) {
                 st_.batches++;
+                if (b->use_geom) st_.geometry_launches++;
                 st_.kernel_s += ms * 1e-3;
                 if (layout >= 0 && layout < 4) st_.launches_by_layout[layout]++;
                 else if (layout >= MVHP_LAYOUT_WIDE && layout <= MVHP_LAYOUT_PIPE1) st_.launches_wide[layout - MVHP_LAYOUT_WIDE]++;
@@ -870,7 +980,10 @@ void Engine::downloader(int k)
             b = batches_[cx.to_download.front()].get();
             cx.to_download.pop_front();
         }
-        const size_t yb = mvhp_yuv_frame_bytes(&b->params), rb = want_rgb_ ? mvhp_rgb_frame_bytes(&b->params) : 0;
+        // a batch with a geometry: only its output pictures come back
+        const size_t yb = b->use_geom ? mvhp_geometry_yuv_bytes(&b->geom) : mvhp_yuv_frame_bytes(&b->params);
+        const size_t rb = !want_rgb_ ? 0 : b->use_geom ? mvhp_geometry_rgb_bytes(&b->geom) : mvhp_rgb_frame_bytes(&b->params);
+        const uint8_t *d_y = b->use_geom ? b->buf->out_yuv : b->buf->yuv, *d_r = b->use_geom ? b->buf->out_rgb : b->buf->rgb;
         const int C = std::min(chunk_pictures(b->params), b->capacity);
         std::string fail;
         for (int g = 0; g < b->total && fail.empty(); g += C) {
@@ -901,8 +1014,8 @@ void Engine::downloader(int k)
                 const void *src[2];
                 size_t nb[2];
                 int np = 0;
-                if (want_yuv_) { dst[np] = oc->yuv.p; src[np] = b->buf->yuv + (size_t)g * yb; nb[np++] = (size_t)n * yb; }
-                if (want_rgb_) { dst[np] = oc->rgb.p; src[np] = b->buf->rgb + (size_t)g * rb; nb[np++] = (size_t)n * rb; }
+                if (want_yuv_) { dst[np] = oc->yuv.p; src[np] = d_y + (size_t)g * yb; nb[np++] = (size_t)n * yb; }
+                if (want_rgb_) { dst[np] = oc->rgb.p; src[np] = d_r + (size_t)g * rb; nb[np++] = (size_t)n * rb; }
                 ok = api_.d2h(cx.dev, np, dst, src, nb, &ms, err) == MVHP_SUCCESS;
             }
             {
@@ -945,9 +1058,14 @@ void Engine::downloader(int k)
 // ---------------------------------------------------------------------------------------------------------------
 // one decode call
 // ---------------------------------------------------------------------------------------------------------------
-int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int wanted, int out_mask, mvhp_picture_sink_t sink,
-                   void *user, mvhp_decode_stats_t *stats, std::string &err)
+int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int wanted, int out_mask, const mvhp_output_request_t *req,
+                   mvhp_picture_sink_t sink, mvhp_picture_sink_ex_t sink_ex, void *user, mvhp_decode_stats_t *stats,
+                   std::string &err)
 {
+    if (req && ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX)) || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2)))) {
+        err = "malformed output request (box sides must be at least 2)";
+        return MVHP_FAILURE;
+    }
     if (!order || n_order <= 0 || wanted <= 0) { err = "nothing to decode"; return MVHP_FAILURE; }
     for (int i = 0; i < n_order; i++)
         if (order[i] < 0 || (size_t)order[i] >= s.idrs.size()) { err = "IDR index out of range"; return MVHP_FAILURE; }
@@ -958,6 +1076,7 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         s_ = &s; order_ = order; n_order_ = n_order; wanted_ = std::min(wanted, n_order);
         want_rgb_ = (out_mask & 1) != 0;
         want_yuv_ = !want_rgb_ || (out_mask & 2) == 0;
+        req_ = req ? *req : mvhp_output_request_t{};
         stop_ = false; sink_waiting_ = false;
         pos_ = issued_ = consumed_ = ok_ = failed_ = 0;
         next_batch_id_ = 0;
@@ -1036,9 +1155,10 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         }
         if (next == 0) first_picture_s_ = now_s() - t_start;
         int verdict = (r.rc == MVHP_SUCCESS) ? 1 : 0;
-        if (sink) {
+        if (sink || sink_ex) {
             const double t0 = now_s();
-            verdict = sink(user, next, r.idr, r.rc, r.err.c_str(), &r.params, r.yuv, r.rgb);
+            verdict = sink_ex ? sink_ex(user, next, r.idr, r.rc, r.err.c_str(), &r.params, &r.geom, r.yuv, r.rgb)
+                              : sink(user, next, r.idr, r.rc, r.err.c_str(), &r.params, r.yuv, r.rgb);
             sink_s += now_s() - t0;
         }
         bool wake = false;
@@ -1119,10 +1239,11 @@ void engine_destroy(Engine *e) { delete e; }
 void engine_release_picture(Engine *e, int seq) { e->release_picture(seq); }
 
 int engine_decode(Engine *e, const mvhp_stream &s, const int *order, int n_order, int wanted, int out_mask,
-                  mvhp_picture_sink_t sink, void *user, mvhp_decode_stats_t *stats, std::string &err)
+                  const mvhp_output_request_t *req, mvhp_picture_sink_t sink, mvhp_picture_sink_ex_t sink_ex, void *user,
+                  mvhp_decode_stats_t *stats, std::string &err)
 {
     if (!e) { err = "no engine"; return MVHP_FAILURE; }
-    return e->decode(s, order, n_order, wanted, out_mask, sink, user, stats, err);
+    return e->decode(s, order, n_order, wanted, out_mask, req, sink, sink_ex, user, stats, err);
 }
 
 } // namespace mvengine
@@ -1165,7 +1286,17 @@ MVHP_EXPORT int mvhp_engine_decode(mvhp_engine_t *h, const mvhp_stream_t *s, con
                                    int want_rgb, mvhp_picture_sink_t sink, void *user, mvhp_decode_stats_t *stats)
 {
     if (!h || !s) return MVHP_FAILURE;
-    const int rc = mvengine::engine_decode(h->e, *s, order, n_order, wanted, want_rgb, sink, user, stats, g_engine_err);
+    const int rc = mvengine::engine_decode(h->e, *s, order, n_order, wanted, want_rgb, nullptr, sink, nullptr, user, stats, g_engine_err);
+    if (rc != MVHP_SUCCESS) fprintf(stderr, "[minivideo] %s\n", g_engine_err.c_str());
+    return rc;
+}
+
+MVHP_EXPORT int mvhp_engine_decode_ex(mvhp_engine_t *h, const mvhp_stream_t *s, const int *order, int n_order, int wanted,
+                                      int want_rgb, const mvhp_output_request_t *req, mvhp_picture_sink_ex_t sink, void *user,
+                                      mvhp_decode_stats_t *stats)
+{
+    if (!h || !s) return MVHP_FAILURE;
+    const int rc = mvengine::engine_decode(h->e, *s, order, n_order, wanted, want_rgb, req, nullptr, sink, user, stats, g_engine_err);
     if (rc != MVHP_SUCCESS) fprintf(stderr, "[minivideo] %s\n", g_engine_err.c_str());
     return rc;
 }

@@ -43,6 +43,13 @@ struct DeviceApi {
     // each in a group of the device's memory regions of its own (mvhp_placed_alloc_sets); ptrs[s * 4 + i]; nullptr = failed
     void  *(*placed_alloc)(DevCtx *c, int sets, const size_t bytes[4], void **ptrs);
     void   (*placed_free)(DevCtx *c, void *arena);
+    // optional (may be NULL: a batch with an output geometry then fails), last so that a positional initialiser of the
+    // operations above still compiles: `recon` without its fused colour epilogue into d_yuv_coded (scratch: planes of the coded
+    // size), the deblocking filter when p asks for it, then mvhp_resample_dev into n pictures of geometry g -- planes into
+    // d_yuv_out and / or RGB into d_rgb_out (either may be NULL)
+    int    (*recon_geometry)(DevCtx *c, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const void *d_compact,
+                             size_t stride, void *d_packed, int n_pictures, uint8_t *d_yuv_coded, uint8_t *d_yuv_out,
+                             uint8_t *d_rgb_out, float *ms, int *layout, int *waves, std::string &err);
 };
 
 class Engine;
@@ -51,8 +58,10 @@ Engine *engine_create(const DeviceApi &api, const mvhp_engine_opts_t *opts, std:
 void    engine_destroy(Engine *e);
 void    engine_release_picture(Engine *e, int seq);
 int     effective_cores();   // hardware threads cut down to the container's CPU quota
+// one of sink / sink_ex (or neither); req NULL or flags 0: pictures of the coded size, the path without a geometry pass
 int     engine_decode(Engine *e, const mvhp_stream &s, const int *order, int n_order, int wanted, int out_mask,
-                      mvhp_picture_sink_t sink, void *user, mvhp_decode_stats_t *stats, std::string &err);
+                      const mvhp_output_request_t *req, mvhp_picture_sink_t sink, mvhp_picture_sink_ex_t sink_ex, void *user,
+                      mvhp_decode_stats_t *stats, std::string &err);
 
 } // namespace mvengine
 

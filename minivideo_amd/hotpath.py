@@ -146,6 +146,8 @@ def lib():
     L.mvhp_set_layout.argtypes = [vp, i32]
     L.mvhp_set_fused_color.restype = i32
     L.mvhp_set_fused_color.argtypes = [vp, i32]
+    L.mvhp_set_crop_copy.restype = i32
+    L.mvhp_set_crop_copy.argtypes = [vp, i32]
     L.mvhp_recon_batch_dev.restype = i32
     L.mvhp_recon_batch_dev.argtypes = [vp, pp, vp, i32, vp, vp, vp]
     L.mvhp_expand_compact_dev.restype = i32
@@ -226,6 +228,10 @@ class HotPath:
 
     def set_fused_color(self, on):
         self._L.mvhp_set_fused_color(self._h, 1 if on else 0)
+
+    def set_crop_copy(self, on):
+        """True (default): crop-only geometries run the copy kernel; False: the general resample kernel.  Speed only."""
+        self._L.mvhp_set_crop_copy(self._h, 1 if on else 0)
 
     # -- host buffers ------------------------------------------------------
     def recon_host(self, params, packed, n_frames, want_rgb=False):
@@ -336,7 +342,7 @@ class DecodeStats(C.Structure):
                 ("d2h_s", C.c_double), ("sink_s", C.c_double), ("stream_bytes", C.c_uint64), ("h2d_bytes", C.c_uint64),
                 ("d2h_bytes", C.c_uint64), ("host_alloc_s", C.c_double), ("dev_alloc_s", C.c_double),
                 ("first_launch_s", C.c_double), ("first_picture_s", C.c_double), ("host_alloc_bytes", C.c_uint64),
-                ("dev_alloc_bytes", C.c_uint64), ("placed_buffers", C.c_uint32), ("reserved", C.c_uint32),
+                ("dev_alloc_bytes", C.c_uint64), ("placed_buffers", C.c_uint32), ("geometry_launches", C.c_uint32),
                 ("launches_wide", C.c_uint32 * 4)]
 
     def as_dict(self):
@@ -351,6 +357,10 @@ SINK_T = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p,
                      C.POINTER(C.c_uint8), C.POINTER(C.c_uint8))
 
 
+SINK_EX_T = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(StreamParams),
+                        C.POINTER(OutputGeometry), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8))
+
+
 class Engine:
     """mvhp_engine_t: host entropy threads -> H2D -> batched kernels -> D2H -> sink, over every context."""
 
@@ -363,6 +373,9 @@ class Engine:
         L.mvhp_engine_decode.restype = C.c_int
         L.mvhp_engine_decode.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, SINK_T,
                                          C.c_void_p, C.POINTER(DecodeStats)]
+        L.mvhp_engine_decode_ex.restype = C.c_int
+        L.mvhp_engine_decode_ex.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
+                                            C.POINTER(OutputRequest), SINK_EX_T, C.c_void_p, C.POINTER(DecodeStats)]
         L.mvhp_engine_release_picture.restype = None
         L.mvhp_engine_release_picture.argtypes = [C.c_void_p, C.c_int]
         o = EngineOpts(contexts, host_threads, batch_pictures, chunk_pictures, fail_context, first_device)
@@ -387,12 +400,31 @@ class Engine:
         """gives back a picture whose sink call answered 2 (any thread; the decode call returns when the last one is back)"""
         self._L.mvhp_engine_release_picture(self._h, int(seq))
 
-    def decode(self, stream_handle, order, wanted=None, want_rgb=False, sink=None):
+    def decode(self, stream_handle, order, wanted=None, want_rgb=False, sink=None, output=None):
         """sink(seq, idr, rc, err, params, yuv ndarray | None, rgb ndarray | None) -> 1 accept / 0 reject / -1 stop /
         2 accept and keep until release_picture(seq); the arrays are views of page-locked memory valid only during the call
-        (or until the release).  Returns (rc, stats dict)."""
+        (or until the release).  Returns (rc, stats dict).
+        output (see output_request()): None = pictures of the coded size (mvhp_engine_decode); "crop" or a (w, h) box =
+        mvhp_engine_decode_ex, and the sink is called with one more argument after params, the picture's OutputGeometry (a
+        copy): sink(seq, idr, rc, err, params, geometry, yuv, rgb), the arrays sized by it."""
         order = (C.c_int * len(order))(*order)
         st = DecodeStats()
+        n_wanted = len(order) if wanted is None else wanted
+        if output is not None:
+            req = output_request(output)
+
+            def _cbx(user, seq, idr, rc, err, p, g, yuv, rgb):
+                if sink is None:
+                    return 1 if rc == SUCCESS else 0
+                pr, geom = p.contents, OutputGeometry.from_buffer_copy(g.contents)
+                y = np.ctypeslib.as_array(yuv, shape=(geom.yuv_bytes,)) if yuv else None
+                r = np.ctypeslib.as_array(rgb, shape=(geom.rgb_bytes,)) if rgb else None
+                return int(sink(seq, idr, rc, err.decode() if err else "", pr, geom, y, r))
+
+            cbx = SINK_EX_T(_cbx) if sink is not None else C.cast(None, SINK_EX_T)
+            rc = self._L.mvhp_engine_decode_ex(self._h, stream_handle, order, len(order), n_wanted, int(want_rgb),
+                                               C.byref(req), cbx, None, C.byref(st))
+            return rc, st.as_dict()
 
         def _cb(user, seq, idr, rc, err, p, yuv, rgb):
             if sink is None:

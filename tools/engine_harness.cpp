@@ -4,7 +4,9 @@
 // lets the sink check that the right picture arrives in the right place, in order, through chunks, batches, several
 // contexts and a re-queue.  Nothing here is part of libminivideo.so.
 //
-// usage: engine_harness <stream.264> <scenario>
+// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes>]]
+// The fourth argument adds the geometry mode: mvhp_engine_decode_ex and minivideo_decode under MINIVIDEO_CROP /
+// MINIVIDEO_THUMBNAIL against the stub's output-geometry operation.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -41,7 +43,7 @@ namespace {
 
 using mvengine::DevCtx;
 
-std::atomic<int> g_recon_calls{0}, g_live_ctx{0};
+std::atomic<int> g_recon_calls{0}, g_live_ctx{0}, g_geometry_calls{0}, g_ctx_created{0};
 std::atomic<long> g_dev_allocs{0};
 int g_devices = 2;
 std::atomic<int> g_slow_host_alloc_us{0};   // page-locking is slow on a real box: the feeder drops its lock around it
@@ -60,7 +62,7 @@ void *stub_host_alloc(size_t n)
     return malloc(n ? n : 1);
 }
 void stub_host_free(void *p) { free(p); }
-DevCtx *stub_ctx_create(int device, std::string &) { g_live_ctx++; return new DevCtx{device}; }
+DevCtx *stub_ctx_create(int device, std::string &) { g_live_ctx++; g_ctx_created++; return new DevCtx{device}; }
 void stub_ctx_destroy(DevCtx *c) { g_live_ctx--; delete c; }
 void *stub_dev_alloc(DevCtx *, size_t n) { g_dev_allocs++; return malloc(n ? n : 1); }
 void stub_dev_free(DevCtx *, void *p) { g_dev_allocs--; free(p); }
@@ -118,9 +120,144 @@ int stub_recon(DevCtx *, const mvhp_stream_params_t *p, const void *d_compact, s
     return MVHP_SUCCESS;
 }
 
+// The output-geometry operation: the coded planes are written in full (the scratch buffer must hold them), every output
+// picture is filled up to its last byte (the output buffers must hold n pictures of the geometry) and stamped: planes
+// 0x5a, checksum of the records in bytes 0-7, 0x77 in the last byte; RGB 0xa5, the checksum in bytes 8-15, 0x78 last.
+constexpr uint8_t kLastYuv = 0x77, kLastRgb = 0x78;
+int stub_recon_geometry(DevCtx *, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const void *d_compact, size_t stride,
+                        void *d_packed, int n, uint8_t *d_yuv_coded, uint8_t *d_yuv_out, uint8_t *d_rgb_out, float *ms, int *layout,
+                        int *waves, std::string &err)
+{
+    g_geometry_calls++;
+    if (!g || !d_yuv_coded || (!d_yuv_out && !d_rgb_out)) { err = "stub: geometry launch without buffers"; return MVHP_FAILURE; }
+    const size_t pb = mvhp_packed_frame_bytes(p), yb = mvhp_yuv_frame_bytes(p);
+    const size_t gy = mvhp_geometry_yuv_bytes(g), gr = mvhp_geometry_rgb_bytes(g);
+    for (int i = 0; i < n; i++)
+        expand_compact((const uint8_t *)d_compact + (size_t)i * stride, (size_t)p->width_mbs * p->height_mbs, (uint8_t *)d_packed + (size_t)i * pb);
+    memset(d_yuv_coded, 0x11, (size_t)n * yb);
+    for (int i = 0; i < n; i++) {
+        const uint64_t h = checksum((const uint8_t *)d_packed + (size_t)i * pb, pb);
+        if (d_yuv_out) {
+            memset(d_yuv_out + (size_t)i * gy, 0x5a, gy);
+            memcpy(d_yuv_out + (size_t)i * gy, &h, sizeof(h));
+            d_yuv_out[(size_t)i * gy + gy - 1] = kLastYuv;
+        }
+        if (d_rgb_out) {
+            memset(d_rgb_out + (size_t)i * gr, 0xa5, gr);
+            memcpy(d_rgb_out + (size_t)i * gr + 8, &h, sizeof(h));
+            d_rgb_out[(size_t)i * gr + gr - 1] = kLastRgb;
+        }
+    }
+    std::this_thread::sleep_for(std::chrono::microseconds(200));
+    if (ms) *ms = 0.2f;
+    if (layout) *layout = MVHP_LAYOUT_ROWS;
+    if (waves) *waves = 8;
+    return MVHP_SUCCESS;
+}
+
 const mvengine::DeviceApi g_stub = {stub_device_count, stub_host_alloc, stub_host_free, stub_ctx_create, stub_ctx_destroy,
                                     stub_dev_alloc, stub_dev_free, stub_dev_free_bytes, stub_copy_n, stub_copy_n, stub_recon,
-                                    nullptr, nullptr};   // (no placed arena on the stub device)
+                                    nullptr, nullptr,   // (no placed arena on the stub device)
+                                    stub_recon_geometry};
+
+uint64_t picture_checksum(const mvhp_stream &s, int idr)
+{
+    mvhp_stream_params_t p;
+    if (mvhp_stream_params(&s, idr, &p) != MVHP_SUCCESS) return 0;
+    std::vector<uint8_t> packed(mvhp_packed_frame_bytes(&p));
+    std::string e;
+    if (s.decode_packed(idr, packed.data(), packed.size(), e) != h264::RC_SUCCESS) return 0;
+    return checksum(packed.data(), packed.size());
+}
+
+// sink of the geometry mode: the right picture, in order, with the geometry mvhp_output_geometry gives for it and buffers that
+// reach to the last byte of that geometry (pictures of the coded size come from stub_recon: no end mark)
+struct CheckG {
+    const mvhp_stream *s = nullptr;
+    mvhp_output_request_t req{};
+    bool want_yuv = true, want_rgb = false;
+    int calls = 0, ok = 0, failed = 0, bad = 0, next_seq = 0, with_geometry = 0;
+    std::vector<int> order;
+    static int sink(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                    const uint8_t *yuv, const uint8_t *rgb)
+    {
+        CheckG &c = *static_cast<CheckG *>(user);
+        c.calls++;
+        if (seq != c.next_seq || idr != c.order[(size_t)seq] || !g) c.bad++;
+        c.next_seq = seq + 1;
+        mvhp_output_geometry_t want;
+        const bool formed = mvhp_output_geometry(c.s, idr, &c.req, &want) == MVHP_SUCCESS;
+        if (rc != MVHP_SUCCESS) {
+            c.failed++;
+            if (!err || !*err || yuv || rgb || formed) c.bad++;   // (the only failures of this mode: a geometry that cannot be formed)
+            return 0;
+        }
+        if (!formed || !g || memcmp(&want, g, sizeof(want)) != 0) { c.bad++; return 0; }
+        const bool coded = g->crop_x == 0 && g->crop_y == 0 && g->out_w == p->width_mbs * 16 && g->out_h == p->height_mbs * 16 &&
+                           g->crop_w == g->out_w && g->crop_h == g->out_h;
+        if (!coded) c.with_geometry++;
+        const uint64_t h = picture_checksum(*c.s, idr);
+        const size_t gy = mvhp_geometry_yuv_bytes(g), gr = mvhp_geometry_rgb_bytes(g);
+        uint64_t got = 0;
+        if (c.want_yuv) {
+            if (!yuv) { c.bad++; return 0; }
+            memcpy(&got, yuv, 8);
+            if (got != h || yuv[8] != 0x5a || yuv[gy - 1] != (coded ? 0x5a : kLastYuv)) c.bad++;
+        } else if (yuv) c.bad++;
+        if (c.want_rgb) {
+            if (!rgb) { c.bad++; return 0; }
+            memcpy(&got, rgb + 8, 8);
+            if (got != h || rgb[0] != 0xa5 || rgb[gr - 1] != (coded ? 0xa5 : kLastRgb)) c.bad++;
+        } else if (rgb) c.bad++;
+        c.ok++;
+        return 1;
+    }
+};
+
+std::vector<uint8_t> read_file(const std::string &path)
+{
+    std::vector<uint8_t> b;
+    FILE *f = fopen(path.c_str(), "rb");
+    uint8_t tmp[65536];
+    for (size_t n; f && (n = fread(tmp, 1, sizeof(tmp), f)) > 0;) b.insert(b.end(), tmp, tmp + n);
+    if (f) fclose(f);
+    return b;
+}
+
+// BMP (24 bit, bottom-up, B G R, rows padded to 4 bytes) / TGA (type 10, bottom row first, B G R) -> top-down R G B of w x h, or empty
+std::vector<uint8_t> bmp_pixels(const std::vector<uint8_t> &f, int w, int h)
+{
+    const size_t row = ((size_t)w * 3 + 3) & ~(size_t)3;
+    uint32_t fw = 0, fh = 0, size = 0;
+    if (f.size() != 54 + row * (size_t)h || f[0] != 'B' || f[1] != 'M') return {};
+    memcpy(&size, &f[2], 4); memcpy(&fw, &f[18], 4); memcpy(&fh, &f[22], 4);
+    if (size != f.size() || fw != (uint32_t)w || fh != (uint32_t)h || f[28] != 24) return {};
+    std::vector<uint8_t> rgb((size_t)w * h * 3);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++)
+            for (int k = 0; k < 3; k++) rgb[((size_t)y * w + x) * 3 + k] = f[54 + (size_t)(h - 1 - y) * row + (size_t)x * 3 + 2 - k];
+    return rgb;
+}
+std::vector<uint8_t> tga_pixels(const std::vector<uint8_t> &f, int w, int h)
+{
+    if (f.size() < 18 || f[2] != 10 || f[16] != 24 || (f[12] | (f[13] << 8)) != w || (f[14] | (f[15] << 8)) != h) return {};
+    std::vector<uint8_t> bgr;
+    size_t at = 18;
+    while (at < f.size() && bgr.size() < (size_t)w * h * 3) {
+        const int n = (f[at] & 127) + 1;
+        const bool run = (f[at] & 128) != 0;
+        at++;
+        if (at + (run ? 3 : (size_t)n * 3) > f.size()) return {};
+        for (int i = 0; i < n; i++) bgr.insert(bgr.end(), &f[at + (run ? 0 : (size_t)i * 3)], &f[at + (run ? 0 : (size_t)i * 3)] + 3);
+        at += run ? 3 : (size_t)n * 3;
+    }
+    if (at != f.size() || bgr.size() != (size_t)w * h * 3) return {};
+    std::vector<uint8_t> rgb(bgr.size());
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++)
+            for (int k = 0; k < 3; k++) rgb[((size_t)y * w + x) * 3 + k] = bgr[((size_t)(h - 1 - y) * w + x) * 3 + 2 - k];
+    return rgb;
+}
 
 struct Check {
     const mvhp_stream *s = nullptr;
@@ -395,6 +532,192 @@ int main(int argc, char **argv)
         unsetenv("MINIVIDEO_WRITERS");
         EXPECT(chdir(cwd) == 0);
         rmdir(dir);
+    }
+    EXPECT(g_geometry_calls == 0);   // nothing above asks for an output geometry
+    if (argc > 4) {   // ---- geometry mode ----
+        std::vector<uint8_t> b3 = read_file(argv[4]);
+        mvhp_stream s3;
+        s3.data = b3.data();
+        s3.size = b3.size();
+        EXPECT(s3.build(err) == h264::RC_SUCCESS);
+        const int n3 = (int)s3.idrs.size();
+        std::vector<int> o3((size_t)n3);
+        for (int i = 0; i < n3; i++) o3[(size_t)i] = i;
+        // what the engine has to form under `req`: runs of equal geometry are batches (the batch size below is larger than any
+        // run), pictures whose geometry is the coded size take the plain operation, those without a geometry fail in place
+        auto expect = [&](const mvhp_stream &st, const std::vector<int> &order, const mvhp_output_request_t &req, int &runs, int &geom_runs, int &unformed) {
+            runs = geom_runs = unformed = 0;
+            mvhp_output_geometry_t prev{};
+            bool have = false;
+            for (int idr : order) {
+                mvhp_output_geometry_t g;
+                mvhp_stream_params_t p;
+                if (mvhp_output_geometry(&st, idr, &req, &g) != MVHP_SUCCESS) { unformed++; continue; }   // (occupies no slot: the run goes on)
+                EXPECT(mvhp_stream_params(&st, idr, &p) == MVHP_SUCCESS);
+                if (!have || memcmp(&prev, &g, sizeof(g)) != 0) {
+                    runs++;
+                    if (!(g.crop_x == 0 && g.crop_y == 0 && g.out_w == p.width_mbs * 16 && g.out_h == p.height_mbs * 16 && g.crop_w == g.out_w && g.crop_h == g.out_h)) geom_runs++;
+                }
+                prev = g;
+                have = true;
+            }
+        };
+        auto run_ex = [&](const char *name, mvhp_engine_opts_t o, const mvhp_stream &st, const std::vector<int> &order, int mask,
+                          const mvhp_output_request_t &req, CheckG &c, mvhp_decode_stats_t &stats) {
+            mvhp_engine_t *e = nullptr;
+            if (mvhp_engine_create(&o, &e) != MVHP_SUCCESS) { failures++; return MVHP_FAILURE; }
+            c.s = &st; c.req = req; c.order = order;
+            c.want_rgb = (mask & 1) != 0;
+            c.want_yuv = !c.want_rgb || (mask & 2) == 0;
+            const int rc = mvhp_engine_decode_ex(e, &st, order.data(), (int)order.size(), (int)order.size(), mask, &req, CheckG::sink, &c, &stats);
+            mvhp_engine_destroy(e);
+            printf("%-28s rc=%d issued=%u ok=%u failed=%u batches=%u geometry=%u requeued=%u d2h=%llu\n", name, rc, stats.pictures_issued,
+                   stats.pictures_ok, stats.pictures_failed, stats.batches, stats.geometry_launches, stats.batches_requeued,
+                   (unsigned long long)stats.d2h_bytes);
+            return rc;
+        };
+        auto d2h_expected = [&](const mvhp_stream &st, const std::vector<int> &order, const mvhp_output_request_t &req, int mask) {
+            uint64_t sum = 0;
+            for (int idr : order) {
+                mvhp_output_geometry_t g;
+                if (mvhp_output_geometry(&st, idr, &req, &g) != MVHP_SUCCESS) continue;
+                if (!(mask & 1) || !(mask & 2)) sum += mvhp_geometry_yuv_bytes(&g);
+                if (mask & 1) sum += mvhp_geometry_rgb_bytes(&g);
+            }
+            return sum;
+        };
+        const mvhp_output_request_t crop{MVHP_OUTPUT_CROP, 0, 0, 0}, box{MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX, 40, 40, 0};
+        for (int mask : {0, MVHP_OUT_RGB, MVHP_OUT_RGB_ONLY})
+            for (const mvhp_output_request_t &req : {crop, box}) {   // batches split where the geometry changes
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 64;
+                CheckG c; mvhp_decode_stats_t st;
+                int runs, geom_runs, unformed;
+                expect(s3, o3, req, runs, geom_runs, unformed);
+                const int before = g_geometry_calls;
+                EXPECT(run_ex(req.flags & MVHP_OUTPUT_BOX ? "geometry box" : "geometry crop", o, s3, o3, mask, req, c, st) == MVHP_SUCCESS);
+                EXPECT(runs >= 4 && geom_runs >= 3 && unformed >= 1);   // (the stream the test wrote mixes crops)
+                EXPECT(c.bad == 0 && c.calls == n3 && c.failed == unformed && c.ok == n3 - unformed);
+                EXPECT((int)st.batches == runs && (int)st.geometry_launches == geom_runs && g_geometry_calls - before == geom_runs);
+                EXPECT(st.d2h_bytes == d2h_expected(s3, o3, req, mask));
+            }
+        {   // small batches inside the runs, three contexts, the first batch of context 0 fails: re-queued with its geometry
+            std::vector<int> order;
+            for (int k = 0; k < 3 * n3; k++) order.push_back(k % n3);
+            mvhp_engine_opts_t o = base; o.contexts = 3; o.chunk_pictures = 2; o.batch_pictures = 3; o.fail_context = 0;
+            CheckG c; mvhp_decode_stats_t st;
+            int runs, geom_runs, unformed;
+            expect(s3, order, box, runs, geom_runs, unformed);
+            EXPECT(run_ex("geometry requeue/3ctx", o, s3, order, MVHP_OUT_RGB, box, c, st) == MVHP_SUCCESS);
+            EXPECT(c.bad == 0 && c.failed == unformed && c.ok == (int)order.size() - unformed && st.batches_requeued == 1);
+            EXPECT((int)st.batches >= runs && st.d2h_bytes == d2h_expected(s3, order, box, MVHP_OUT_RGB));
+        }
+        {   // requests that equal the coded size -- a crop of an uncropped stream, a box that already contains it -- never call the
+            // geometry operation
+            const int before = g_geometry_calls;
+            for (const mvhp_output_request_t &req : {crop, mvhp_output_request_t{MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX, 4096, 4096, 0}}) {
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 3; o.batch_pictures = 7;
+                CheckG c; mvhp_decode_stats_t st;
+                EXPECT(run_ex("geometry = coded size", o, s, all, MVHP_OUT_RGB, req, c, st) == MVHP_SUCCESS);
+                EXPECT(c.bad == 0 && c.ok == n_idr && c.with_geometry == 0 && st.geometry_launches == 0);
+            }
+            EXPECT(g_geometry_calls == before);
+        }
+        {   // a malformed request is refused
+            mvhp_engine_opts_t o = base; o.contexts = 1;
+            mvhp_engine_t *e = nullptr;
+            EXPECT(mvhp_engine_create(&o, &e) == MVHP_SUCCESS);
+            const mvhp_output_request_t bad{MVHP_OUTPUT_BOX, 1, 40, 0};
+            mvhp_decode_stats_t st;
+            EXPECT(mvhp_engine_decode_ex(e, &s3, o3.data(), n3, n3, 0, &bad, nullptr, nullptr, &st) == MVHP_FAILURE);
+            mvhp_engine_destroy(e);
+        }
+        {   // minivideo_decode under MINIVIDEO_CROP / MINIVIDEO_THUMBNAIL: files of the output geometry, the stub's stamps in place
+            char tmpl[] = "/tmp/mvharness_XXXXXX";
+            const char *dir = mkdtemp(tmpl);
+            char cwd[4096];
+            EXPECT(dir != nullptr && getcwd(cwd, sizeof(cwd)) != nullptr);
+            std::string in = argv[4];
+            if (in[0] != '/') in = std::string(cwd) + "/" + in;
+            EXPECT(dir && chdir(dir) == 0);
+            struct Sw { const char *crop, *thumb; mvhp_output_request_t req; };
+            const Sw sws[] = {{"1", nullptr, crop}, {nullptr, "40x40", box}, {"1", "40x40", box}, {"0", nullptr, mvhp_output_request_t{}}};
+            for (const Sw &sw : sws)
+                for (int fmt : {PICTURE_YUV420, PICTURE_BMP, PICTURE_TGA})
+                    for (const char *writers : {"2", "0"}) {
+                        setenv("MINIVIDEO_WRITERS", writers, 1);
+                        if (sw.crop) setenv("MINIVIDEO_CROP", sw.crop, 1); else unsetenv("MINIVIDEO_CROP");
+                        if (sw.thumb) setenv("MINIVIDEO_THUMBNAIL", sw.thumb, 1); else unsetenv("MINIVIDEO_THUMBNAIL");
+                        MediaFile_t *m = nullptr;
+                        EXPECT(minivideo_open(in.c_str(), &m) == SUCCESS);
+                        EXPECT(m && minivideo_parse(m, false, true, false) == SUCCESS);
+                        EXPECT(m && minivideo_decode(m, ".", fmt, 75, n3, PICTURE_UNFILTERED) == SUCCESS);
+                        const char *ext = fmt == PICTURE_BMP ? ".bmp" : fmt == PICTURE_TGA ? ".tga" : ".yuv";
+                        int files = 0, good = 0, k = 0, expected = 0;
+                        for (int idr = 0; idr < n3; idr++) {   // pictures without a geometry are skipped: file k is the k-th good one
+                            mvhp_output_geometry_t g;
+                            mvhp_stream_params_t p;
+                            if (mvhp_output_geometry(&s3, idr, &sw.req, &g) != MVHP_SUCCESS) continue;
+                            expected++;
+                            EXPECT(mvhp_stream_params(&s3, idr, &p) == MVHP_SUCCESS);
+                            const bool coded = g.crop_x == 0 && g.crop_y == 0 && g.out_w == p.width_mbs * 16 && g.out_h == p.height_mbs * 16 &&
+                                               g.crop_w == g.out_w && g.crop_h == g.out_h;
+                            const std::string name = std::string(m->file_name) + "_" + std::to_string(k++) + ext;
+                            const std::vector<uint8_t> f = read_file(name);
+                            if (f.empty()) continue;
+                            files++;
+                            remove(name.c_str());
+                            const uint64_t h = picture_checksum(s3, idr);
+                            const int w = (int)g.out_w, ht = (int)g.out_h;
+                            uint64_t got = 0;
+                            if (fmt == PICTURE_YUV420) {
+                                if (f.size() != mvhp_geometry_yuv_bytes(&g)) continue;
+                                memcpy(&got, f.data(), 8);
+                                if (got == h && f[8] == 0x5a && f.back() == (coded ? 0x5a : kLastYuv)) good++;
+                            } else {
+                                const std::vector<uint8_t> rgb = fmt == PICTURE_BMP ? bmp_pixels(f, w, ht) : tga_pixels(f, w, ht);
+                                if (rgb.size() != mvhp_geometry_rgb_bytes(&g)) continue;
+                                memcpy(&got, rgb.data() + 8, 8);
+                                if (got == h && rgb[0] == 0xa5 && rgb.back() == (coded ? 0xa5 : kLastRgb)) good++;
+                            }
+                        }
+                        printf("%-28s crop=%s thumbnail=%s format=%d writers=%s files=%d of %d, right in %d\n", "public API, geometry",
+                               sw.crop ? sw.crop : "-", sw.thumb ? sw.thumb : "-", fmt, writers, files, expected, good);
+                        EXPECT(expected >= 4 && files == expected && good == expected);
+                        EXPECT(minivideo_close(&m) == SUCCESS);
+                    }
+            // malformed values: FAILURE, with a message, before the device is touched
+            unsetenv("MINIVIDEO_CROP");
+            for (const char *bad : {"abc", "0x10", "320", "1x40", "40x1", "40x", "x40", "40x40x", " 40x40", "40X40", "-4x40", "40x99999"}) {
+                setenv("MINIVIDEO_THUMBNAIL", bad, 1);
+                MediaFile_t *m = nullptr;
+                EXPECT(minivideo_open(in.c_str(), &m) == SUCCESS);
+                EXPECT(m && minivideo_parse(m, false, true, false) == SUCCESS);
+                const int ctx_before = g_ctx_created, recon_before = g_recon_calls + g_geometry_calls;
+                fflush(stdout);
+                fflush(stderr);
+                int pipefd[2];
+                EXPECT(pipe(pipefd) == 0);
+                const int saved = dup(2);
+                dup2(pipefd[1], 2);
+                const int rc = m ? minivideo_decode(m, ".", PICTURE_YUV420, 75, n3, PICTURE_UNFILTERED) : SUCCESS;
+                fflush(stderr);
+                dup2(saved, 2);
+                close(saved);
+                close(pipefd[1]);
+                char msg[512] = "";
+                const ssize_t got = read(pipefd[0], msg, sizeof(msg) - 1);
+                close(pipefd[0]);
+                printf("%-28s '%s' rc=%d message: %s", "malformed thumbnail", bad, rc, got > 0 ? msg : "(none)\n");
+                EXPECT(rc == FAILURE && got > 0 && strstr(msg, "MINIVIDEO_THUMBNAIL") != nullptr);
+                EXPECT(g_ctx_created == ctx_before && g_recon_calls + g_geometry_calls == recon_before);
+                EXPECT(minivideo_close(&m) == SUCCESS);
+            }
+            unsetenv("MINIVIDEO_THUMBNAIL");
+            unsetenv("MINIVIDEO_WRITERS");
+            EXPECT(chdir(cwd) == 0);
+            rmdir(dir);
+        }
+        printf("GEOMETRY MODE DONE\n");
     }
     EXPECT(g_live_ctx == 0 && g_dev_allocs == 0);
     printf(failures ? "HARNESS FAILED (%d)\n" : "HARNESS OK\n", failures);

@@ -1,6 +1,9 @@
 // tools/mini_thumbnailer.cpp -- a small thumbnailer CLI over libminivideo's public API with the
 // same options as the reference's mini_thumbnailer (mini_thumbnailer/src/main.cpp:47-302):
 //   -i <file> [-o <dir>] [-f jpg|png|bmp|tga|yuv420|yuv444] [-q 1..99] [-n 1..999] [-e unfiltered|ordered|distributed]
+// plus two of its own, which set the library's opt-in switches (include/minivideo.h) before the decode call:
+//   -c            pictures are the SPS's cropped rectangle (MINIVIDEO_CROP=1)
+//   -s <w>x<h>    ... fitted into a w x h box, never enlarged (MINIVIDEO_THUMBNAIL=<w>x<h>; implies -c)
 // The stock mini_thumbnailer also builds unchanged against include/minivideo.h; this file exists so
 // that the GPU box (which has no copy of the reference) has a CLI to run.
 #include <minivideo.h>
@@ -56,12 +59,14 @@ int main(int argc, char *argv[])
             else if (!strcmp(e, "ordered")) mode = PICTURE_ORDERED;
             else if (!strcmp(e, "distributed")) mode = PICTURE_DISTRIBUTED;
             else fprintf(stderr, "-e : No valid extraction mode specified\n");
-        } else if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) help = true;
+        } else if (!strcmp(argv[i], "-c")) setenv("MINIVIDEO_CROP", "1", 1);
+        else if (!strcmp(argv[i], "-s") && has) setenv("MINIVIDEO_THUMBNAIL", argv[++i], 1);   // (the library checks the value)
+        else if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) help = true;
         else fprintf(stderr, "* Unknown argument '%s'\n", argv[i]);
     }
     if (!in || help) {
         printf("* Usage:\nmini_thumbnailer -i <filepath> [-o <directory>] [-f picture_format][-q picture_quality]"
-               "[-n picture_number] [-e extraction_mode]\n");
+               "[-n picture_number] [-e extraction_mode] [-c] [-s <width>x<height>]\n");
         return EXIT_FAILURE;
     }
     mark("main, arguments read");

@@ -1,6 +1,8 @@
 """Cost of the output-geometry pass (resample.hip): a batch of 1080p pictures (Baseline and High, the shapes of bench.py's
 2048 x 1080p configurations) on the same device buffers -- the default launch (planes + fused RGB), planes-only reconstruction
-followed by a 320 x 320 thumbnail (planes + RGB), and the resample kernel alone (crop only, and the 320 x 180 thumbnail).  Warm-up
+followed by a 320 x 320 thumbnail (planes + RGB), the resample kernel alone (the 320 x 180 thumbnail), and crop only (1920 x 1080
+out of 1920 x 1088) on both kernels that can do it -- the copy kernel (crop_copy.hip) and the general resample kernel
+(mvhp_set_crop_copy(ctx, 0)) -- with planes, with RGB and with both ("crop_only" in the result).  Warm-up
 launches, then several timed launches bracketed by HIP events; medians.  Bytes moved by the resample kernel alone are computed
 from the shapes (every cropped source sample read once, every output byte written once).
 
@@ -73,7 +75,21 @@ def main():
             hot.resample_dev(params, thumb, Y, n, d_ty.data_ptr(), d_tr.data_ptr(), s)
         r_thumb = timed(planes_then_thumb)
         r_rs = timed(lambda: hot.resample_dev(params, thumb, Y, n, d_ty.data_ptr(), d_tr.data_ptr(), s))
-        r_crop = timed(lambda: hot.resample_dev(params, crop, Y, n, d_cy.data_ptr(), None, s))
+        # crop only on both kernels, the same buffers: the copy kernel (what mvhp_resample_dev chooses) and the general
+        # resample kernel (mvhp_set_crop_copy(ctx, 0)); planes, RGB, and both
+        d_cr = torch.empty(n * crop.rgb_bytes, dtype=torch.uint8, device=dev)
+        crop_only = {}
+        for kernel, on in (("copy", True), ("general", False)):
+            hot.set_crop_copy(on)
+            for what, yo, ro in (("planes", d_cy.data_ptr(), None), ("rgb", None, d_cr.data_ptr()),
+                                 ("planes_rgb", d_cy.data_ptr(), d_cr.data_ptr())):
+                r = timed(lambda: hot.resample_dev(params, crop, Y, n, yo, ro, s))
+                wrote = n * ((crop.yuv_bytes if yo else 0) + (crop.rgb_bytes if ro else 0))
+                crop_only[kernel + "_" + what] = {"ms": r[0], "min_max": r[1:],
+                                                  "TBps": round((n * crop.yuv_bytes + wrote) / (r[0] * 1e-3) / 1e12, 2)}
+        hot.set_crop_copy(True)
+        r_crop = (crop_only["copy_planes"]["ms"],) + tuple(crop_only["copy_planes"]["min_max"])
+        del d_cr
         read = n * 1920 * 1080 * 3 // 2
         thumb_bytes = read + n * (thumb.yuv_bytes + thumb.rgb_bytes)
         crop_bytes = read + n * crop.yuv_bytes
@@ -81,6 +97,7 @@ def main():
                            "resample_thumbnail_alone_ms": r_rs[0], "resample_crop_only_ms": r_crop[0],
                            "resample_thumbnail_TBps": round(thumb_bytes / (r_rs[0] * 1e-3) / 1e12, 2),
                            "resample_crop_TBps": round(crop_bytes / (r_crop[0] * 1e-3) / 1e12, 2),
+                           "crop_only": crop_only,
                            "min_max": {"default": r_default[1:], "thumb": r_thumb[1:], "resample": r_rs[1:], "crop": r_crop[1:]}}
         del d_packed, d_yuv, d_rgb, d_ty, d_tr, d_cy
         torch.cuda.empty_cache()
