@@ -7,6 +7,8 @@ answer UNSUPPORTED :904-923; I_PCM answers UNSUPPORTED h264_macroblock.c:151-154
   id per macroblock, its own reading of Table 7-2's fall-back rules, its own I_PCM writer incl. the CABAC flush / restart);
 * hand-derived samples for the reconstruction rules (derivations below), checked on the oracle (CPU) and on the kernels (GPU);
 * HIP against the oracle on generated streams, through the record path and through the engine.
+* beyond these, oracle and kernels are held to an independent model of the standard: tests/spec_model.py, tests/test_spec_model.py
+  (which also runs the hand vectors below on the model) and tests/test_gpu_spec_model.py.
 
 Hand derivations (Appendix-A macroblock: Intra16x16, DC prediction, one luma DC level +3, QP'Y 28, nothing else coded):
   f = 3 at all 16 positions of the DC matrix; qP = 28 < 36: dcY = (f * LevelScale(28 % 6 = 4, 0, 0) + 2^(5 - 4)) >> (6 - 4).
