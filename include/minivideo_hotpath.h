@@ -300,11 +300,13 @@ MVHP_EXPORT int  mvhp_recon_batch_host(mvhp_ctx_t *ctx, const mvhp_stream_params
                                        const void *h_packed, int n_frames,
                                        uint8_t *h_yuv, uint8_t *h_rgb);
 
-/* Test hook: the next launch of a wide kernel form hands out its work units `delta` off (see hotpath_abi.hip).  Never in products. */
+/* Test hook: the next launch of a banded kernel form hands out its work units `delta` off (see hotpath_abi.hip).  Never in products. */
 MVHP_EXPORT int  mvhp_debug_skew_next_ticket_base(mvhp_ctx_t *ctx, int delta);
 
-/* What the last reconstruction launch of this context used (speed-only choices of the launcher):
- * *layout = MVHP_LAYOUT_ROWS/QUAD/OCT, *waves = wavefronts per workgroup.  Either pointer may be NULL. */
+/* What the last reconstruction launch of this context used (speed-only choices of the launch planner, see mvhp_plan_launch):
+ * *layout = the kernel form that ran, MVHP_LAYOUT_ROWS .. MVHP_LAYOUT_PIPE1 (never MVHP_LAYOUT_AUTO); *waves = wavefronts per
+ * workgroup (ROWS, QUAD, OCT) or macroblock rows per band (WIDE, QUAD_WIDE; PIPE, PIPE1: three wavefronts per row).  Either
+ * pointer may be NULL. */
 MVHP_EXPORT int  mvhp_last_launch_info(const mvhp_ctx_t *ctx, int *layout, int *waves);
 
 /* 1 (default): the reconstruction kernel converts to RGB in its epilogue when d_rgb is given;
@@ -316,24 +318,28 @@ MVHP_EXPORT int  mvhp_set_fused_color(mvhp_ctx_t *ctx, int on);
  * for which such a geometry is one tap of 2^14 per axis, i.e. the same bytes.  Speed only, never results. */
 MVHP_EXPORT int  mvhp_set_crop_copy(mvhp_ctx_t *ctx, int on);
 
-/* Tuning knob (speed only, never results): waves per picture workgroup
- * (4, 6, 8, 12 or 16; a layout that is not built for the value takes the next smaller one);
- * 0 = choose from batch size. */
+/* Tuning knob (speed only, never results): waves per picture workgroup, or macroblock rows per band of the banded forms
+ * (1, 2, 4, 6, 8, 12 or 16; a layout that is not built for the value takes the next smaller one it is built for, or its
+ * smallest); 0 = choose from batch size. */
 MVHP_EXPORT int  mvhp_set_waves_per_picture(mvhp_ctx_t *ctx, int waves);
 
-/* Tuning knob (speed only, never results): how pictures map onto workgroups.
- * MVHP_LAYOUT_ROWS: one picture per workgroup, one wavefront per macroblock row (fills the chip from
- * ~256 pictures); MVHP_LAYOUT_QUAD: four pictures per workgroup, 16 lanes per picture (fewer
- * instructions per macroblock, wants >= ~768 pictures); MVHP_LAYOUT_OCT: eight pictures per workgroup, 8 lanes per
- * picture (fewest instructions, wants >= ~2048 pictures); MVHP_LAYOUT_AUTO chooses from the batch size. */
+/* Tuning knob (speed only, never results): how pictures map onto workgroups, seven kernel forms.
+ * MVHP_LAYOUT_AUTO chooses among all seven from the device's size, the picture shape, the flags and the batch size
+ * (mvhp_plan_launch says what it would take).  A forced form that cannot run a batch -- line buffers that do
+ * not fit in LDS, pictures with slices / scaling matrices on a form other than ROWS, WIDE or PIPE1 -- is replaced by the next
+ * one that can.
+ * MVHP_LAYOUT_ROWS: one picture per workgroup, one wavefront per macroblock row; MVHP_LAYOUT_QUAD: four pictures per
+ * workgroup, 16 lanes per picture (fewer instructions per macroblock; a full round is 4 x CUs pictures); MVHP_LAYOUT_OCT:
+ * eight pictures per workgroup, 8 lanes per picture (fewest instructions; whole rounds of 8 x CUs pictures). */
 #define MVHP_LAYOUT_AUTO 0
 #define MVHP_LAYOUT_ROWS 1
 #define MVHP_LAYOUT_QUAD 2
 #define MVHP_LAYOUT_OCT  3
 /* The "wide" forms spread ONE picture (one group of four) over several workgroups -- bands of macroblock rows on different
  * CUs, the rows between two bands handed over through global memory -- so that a handful of pictures fills the chip:
- * MVHP_LAYOUT_WIDE = the one-picture kernel in bands (1 .. ~64 pictures; also every small batch with slices / scaling
- * matrices), MVHP_LAYOUT_QUAD_WIDE = the four-picture kernel in bands (up to ~1024 pictures). */
+ * MVHP_LAYOUT_WIDE = the one-picture kernel in bands (High batches between PIPE1's and QUAD_WIDE's ranges; larger batches
+ * with slices / scaling matrices), MVHP_LAYOUT_QUAD_WIDE = the four-picture kernel in bands (up to about a round of QUAD,
+ * and ragged batches beyond one). */
 #define MVHP_LAYOUT_WIDE      4
 #define MVHP_LAYOUT_QUAD_WIDE 5
 /* MVHP_LAYOUT_PIPE: four pictures over several workgroups as QUAD_WIDE, and every macroblock row worked on by THREE wavefronts
@@ -344,6 +350,17 @@ MVHP_EXPORT int  mvhp_set_waves_per_picture(mvhp_ctx_t *ctx, int waves);
 #define MVHP_LAYOUT_PIPE1     7
 #define MVHP_LAYOUT_COUNT     8
 MVHP_EXPORT int  mvhp_set_layout(mvhp_ctx_t *ctx, int layout);
+
+typedef struct mvhp_plan_device {
+    int32_t  n_cus;            /* compute units                                                      */
+    uint64_t max_lds_bytes;    /* LDS a workgroup may use                                            */
+    int32_t  layout;           /* forced MVHP_LAYOUT_*, MVHP_LAYOUT_AUTO = choose                    */
+    int32_t  waves;            /* forced value of mvhp_set_waves_per_picture, 0 = choose             */
+} mvhp_plan_device_t;
+/* What a reconstruction launch of n_frames pictures would run on: exactly one of ctx / dev is non-NULL (ctx: that context's
+ * device and forced settings).  Pure host arithmetic: needs no HIP device, launches nothing.  Speed only. */
+MVHP_EXPORT int  mvhp_plan_launch(const mvhp_ctx_t *ctx, const mvhp_plan_device_t *dev, const mvhp_stream_params_t *p,
+                                  int n_frames, int *layout, int *waves);
 
 /* ---------------------------------------------------------------------------
  * Decode engine: the whole split path as one pipelined call --

@@ -53,10 +53,12 @@ struct ColorArgs {
     int            width_mbs, height_mbs, n_frames;
 };
 
+// Every launcher: a.n_frames pictures with nw waves per workgroup (the banded forms: nw rows per band); hipErrorInvalidValue
+// for an nw the kernel is not built for (launch_plan.hip: kernel_form) or, banded forms, without ticket counter / epoch / seams.
 size_t     recon_lds_bytes(int width_mbs, int nw);
-hipError_t launch_recon(const ReconArgs &a, int n_frames, int nw, hipStream_t stream);
+hipError_t launch_recon(const ReconArgs &a, int nw, hipStream_t stream);
 // the same kernel with a picture's rows in bands of `nw` (4) over several workgroups (wide_* and seam of ReconArgs set)
-hipError_t launch_recon_wide(const ReconArgs &a, int n_frames, int nw, hipStream_t stream);
+hipError_t launch_recon_wide(const ReconArgs &a, int nw, hipStream_t stream);
 // four pictures per workgroup, 16 lanes per picture (recon_quad.hip)
 size_t     recon_quad_lds_bytes(int width_mbs, int nw);
 hipError_t launch_recon_quad(const ReconArgs &a, int nw, hipStream_t stream);

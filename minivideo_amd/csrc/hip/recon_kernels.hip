@@ -571,24 +571,24 @@ static hipError_t launch_rows_one(const ReconArgs &a, int n_groups, size_t lds, 
 }
 
 // one workgroup per (picture, band of nw rows); a.wide_ticket / wide_base / wide_epoch / seam set by the caller
-hipError_t launch_recon_wide(const ReconArgs &a, int n_frames, int nw, hipStream_t stream)
+hipError_t launch_recon_wide(const ReconArgs &a, int nw, hipStream_t stream)
 {
     if (nw != 4 || !a.wide_ticket || !a.wide_epoch) return hipErrorInvalidValue;
     const int bands = (a.height_mbs + nw - 1) / nw;
     if (bands > 1 && !a.seam) return hipErrorInvalidValue;
     const size_t lds = recon_lds_bytes(a.width_mbs, nw);
     const bool ext = a.slices || a.scaling;
-    return ext ? launch_rows_one<4, true, true>(a, n_frames * bands, lds, stream) : launch_rows_one<4, false, true>(a, n_frames * bands, lds, stream);
+    return ext ? launch_rows_one<4, true, true>(a, a.n_frames * bands, lds, stream) : launch_rows_one<4, false, true>(a, a.n_frames * bands, lds, stream);
 }
 
-hipError_t launch_recon(const ReconArgs &a, int n_frames, int nw, hipStream_t stream)
+hipError_t launch_recon(const ReconArgs &a, int nw, hipStream_t stream)
 {
     const size_t lds = recon_lds_bytes(a.width_mbs, nw);
     const bool ext = a.slices || a.scaling;
     switch (nw) {
-    case 4: return ext ? launch_rows_one<4, true>(a, n_frames, lds, stream) : launch_rows_one<4, false>(a, n_frames, lds, stream);
-    case 8: return ext ? launch_rows_one<8, true>(a, n_frames, lds, stream) : launch_rows_one<8, false>(a, n_frames, lds, stream);
-    case 16: return ext ? launch_rows_one<16, true>(a, n_frames, lds, stream) : launch_rows_one<16, false>(a, n_frames, lds, stream);
+    case 4: return ext ? launch_rows_one<4, true>(a, a.n_frames, lds, stream) : launch_rows_one<4, false>(a, a.n_frames, lds, stream);
+    case 8: return ext ? launch_rows_one<8, true>(a, a.n_frames, lds, stream) : launch_rows_one<8, false>(a, a.n_frames, lds, stream);
+    case 16: return ext ? launch_rows_one<16, true>(a, a.n_frames, lds, stream) : launch_rows_one<16, false>(a, a.n_frames, lds, stream);
     default: return hipErrorInvalidValue;
     }
 }

@@ -113,6 +113,20 @@ def output_geometry(stream_handle, idr, output):
     return g if rc == SUCCESS else None
 
 
+class PlanDevice(C.Structure):
+    """mvhp_plan_device_t: what the launch planner needs to know of a device, and the forced settings (0 = choose)"""
+    _fields_ = [("n_cus", C.c_int32), ("max_lds_bytes", C.c_uint64), ("layout", C.c_int32), ("waves", C.c_int32)]
+
+
+def plan_launch(dev, params, n_frames):
+    """mvhp_plan_launch for a described device (no GPU needed): (layout name, waves per workgroup) a launch of n_frames
+    pictures would run on, or None for malformed arguments"""
+    lay, nw = C.c_int(0), C.c_int(0)
+    if lib().mvhp_plan_launch(None, C.byref(dev), C.byref(params), int(n_frames), C.byref(lay), C.byref(nw)) != SUCCESS:
+        return None
+    return LAYOUTS[lay.value], nw.value
+
+
 def lib_path():
     # MINIVIDEO_LIB: developer override used for A/B experiments with alternative builds of the same library
     return os.environ.get("MINIVIDEO_LIB") or os.path.join(_HERE, "libminivideo.so")
@@ -160,6 +174,8 @@ def lib():
     L.mvhp_sync_check.argtypes = [vp, vp]
     L.mvhp_last_launch_info.restype = i32
     L.mvhp_last_launch_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.mvhp_plan_launch.restype = i32
+    L.mvhp_plan_launch.argtypes = [vp, C.POINTER(PlanDevice), pp, i32, C.POINTER(i32), C.POINTER(i32)]
     pg, u32 = C.POINTER(OutputGeometry), C.c_uint32
     L.mvhp_stream_crop.restype = i32
     L.mvhp_stream_crop.argtypes = [vp, i32, pg]
@@ -220,8 +236,11 @@ class HotPath:
             raise MiniVideoError("waves per picture must be 0 (auto), 1, 2, 4, 6, 8, 12 or 16")
 
     def set_layout(self, layout):
-        """0 auto, 1 one picture per workgroup (rows), 2 four pictures per workgroup (quad), 3 eight (oct), 4 one picture over
-        several workgroups (wide), 5 four pictures over several workgroups (quad_wide); speed only."""
+        """A name of LAYOUTS or its index (MVHP_LAYOUT_*): 0 auto, 1 one picture per workgroup (rows), 2 four pictures per
+        workgroup (quad), 3 eight (oct), 4 one picture over several workgroups (wide), 5 four pictures over several workgroups
+        (quad_wide), 6 the same with three wavefronts per macroblock row (pipe), 7 one picture per wavefront, three wavefronts
+        per row (pipe1); speed only.  A form that cannot run the batch (line buffers that do not fit in LDS, slices / scaling
+        matrices) is replaced: plan_launch() says by which."""
         code = LAYOUTS.index(layout) if layout in LAYOUTS else layout
         if self._L.mvhp_set_layout(self._h, int(code)) != SUCCESS:
             raise ValueError("layout must be one of " + "/".join(LAYOUTS))
@@ -275,6 +294,13 @@ class HotPath:
     def sync_check(self, stream=None):
         if self._L.mvhp_sync_check(self._h, stream) != SUCCESS:
             raise _err(self._L, "mvhp_sync_check")
+
+    def plan_launch(self, params, n_frames):
+        """(layout name, waves per workgroup) the next reconstruction launch of n_frames pictures would use on this context"""
+        lay, nw = C.c_int(0), C.c_int(0)
+        if self._L.mvhp_plan_launch(self._h, None, C.byref(params), int(n_frames), C.byref(lay), C.byref(nw)) != SUCCESS:
+            raise MiniVideoError("mvhp_plan_launch: invalid argument")
+        return LAYOUTS[lay.value], nw.value
 
     def last_launch(self):
         """(layout name, waves per workgroup) of the last reconstruction launch -- speed-only choices of the launcher."""

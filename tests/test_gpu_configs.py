@@ -99,7 +99,7 @@ def _tile_on_device(torch, packed, n):
     return d
 
 
-# pictures per launch -> the kernel pick_layout takes on a 256-CU MI355X for Baseline pictures (hotpath_abi.hip: three waves per
+# pictures per launch -> the kernel pick_layout takes on a 256-CU MI355X for Baseline pictures (launch_plan.hip: three waves per
 # row of ONE picture up to 18 x CUs row-waves = 67 pictures, of four pictures up to 1.15 x CUs pictures, the plain banded form up to
 # 0.84 x 4 x CUs, then one workgroup per four pictures up to a full round of 4 x CUs, beyond that whichever of the banded form (linear in the
 # pictures), rounds of four and rounds of eight per CU the round model makes the shortest)

@@ -63,7 +63,7 @@ def test_kernels_equal_reference_decoder(hot, cid):
 # ---- batches of distinct neighbours through the automatic choice ----
 
 # batch sizes: ints are pictures, floats multiples of the device's CUs (made odd, so that no size is a multiple of four or
-# eight), on both sides of pick_layout's thresholds (hotpath_abi.hip).  With C CUs, rows of 5 macroblocks: High, 17 rows: pipe1
+# eight), on both sides of pick_layout's thresholds (launch_plan.hip).  With C CUs, rows of 5 macroblocks: High, 17 rows: pipe1
 # up to 46 C row-waves (2.7 C pictures), quad_wide up to 3.36 C pictures, quad above, quad_wide again beyond 4 C; 68 rows:
 # wide between 46 C and 76 C row-waves; Baseline: pipe for one picture, pipe1 up to 18 C row-waves (1.06 C pictures), pipe up
 # to 2 C, quad_wide up to 3.36 C, quad, quad_wide again beyond 4 C, oct from about 6.8 C
