@@ -303,6 +303,18 @@ MVHP_EXPORT int  mvhp_recon_batch_host(mvhp_ctx_t *ctx, const mvhp_stream_params
 /* Test hook: the next launch of a banded kernel form hands out its work units `delta` off (see hotpath_abi.hip).  Never in products. */
 MVHP_EXPORT int  mvhp_debug_skew_next_ticket_base(mvhp_ctx_t *ctx, int delta);
 
+/* Test hook: waits for every launch issued on the context, then sets the ticket counter of the banded kernel forms (the device
+ * word and the host's mirror of it) to `ticket` and the epoch tag of the last banded launch to `epoch`: the next banded launch
+ * hands out its units from `ticket` and tags its seams epoch + 1 -- or, after 0xFFFFFFFF, zeroes the seams and starts again at 1.
+ * The seam buffer is left as it is, tags of earlier launches included.  Never in products. */
+MVHP_EXPORT int  mvhp_debug_set_wide_state(mvhp_ctx_t *ctx, uint32_t ticket, uint32_t epoch);
+
+/* Test hook: waits in the same way, then reports the device's ticket counter, the host's mirror of it (equal once every banded
+ * launch has run: one ticket per workgroup), the epoch tag of the last banded launch and the size of the seam buffer.  Any out
+ * pointer may be NULL.  Never in products. */
+MVHP_EXPORT int  mvhp_debug_get_wide_state(mvhp_ctx_t *ctx, uint32_t *device_ticket, uint32_t *ticket_base, uint32_t *epoch,
+                                           size_t *seam_bytes);
+
 /* What the last reconstruction launch of this context used (speed-only choices of the launch planner, see mvhp_plan_launch):
  * *layout = the kernel form that ran, MVHP_LAYOUT_ROWS .. MVHP_LAYOUT_PIPE1 (never MVHP_LAYOUT_AUTO); *waves = wavefronts per
  * workgroup (ROWS, QUAD, OCT) or macroblock rows per band (WIDE, QUAD_WIDE; PIPE, PIPE1: three wavefronts per row).  Either

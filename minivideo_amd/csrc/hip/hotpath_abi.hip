@@ -490,6 +490,41 @@ MVHP_EXPORT int mvhp_debug_skew_next_ticket_base(mvhp_ctx_t *c, int delta)
     return MVHP_SUCCESS;
 }
 
+// Every launch issued on the context has run: the last banded one (it may be on a caller's stream) and the context's own stream.
+static int wide_drain(mvhp_ctx *c)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(c->wide_done));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MVHP_SUCCESS;
+}
+
+/* Test hook (tests/test_gpu_wide_wrap.py): puts the ticket counter and the epoch tag where 2^32 tickets / launches would have
+ * taken them, so that a CORRECT launch runs across a wraparound.  The seams keep the tags of earlier launches: discarding them
+ * is wide_prepare()'s business. */
+MVHP_EXPORT int mvhp_debug_set_wide_state(mvhp_ctx_t *c, uint32_t ticket, uint32_t epoch)
+{
+    if (!c) return MVHP_FAILURE;
+    if (wide_drain(c) != MVHP_SUCCESS) return MVHP_FAILURE;
+    HIP_TRY(hipMemcpy(c->d_ticket, &ticket, sizeof(ticket), hipMemcpyHostToDevice));
+    c->ticket_base = ticket;
+    c->wide_epoch = epoch;
+    return MVHP_SUCCESS;
+}
+
+/* Test hook (tests/test_gpu_wide_wrap.py): the counter on the device beside the host's bookkeeping of it. */
+MVHP_EXPORT int mvhp_debug_get_wide_state(mvhp_ctx_t *c, uint32_t *device_ticket, uint32_t *ticket_base, uint32_t *epoch,
+                                          size_t *seam_bytes)
+{
+    if (!c) return MVHP_FAILURE;
+    if (wide_drain(c) != MVHP_SUCCESS) return MVHP_FAILURE;
+    if (device_ticket) HIP_TRY(hipMemcpy(device_ticket, c->d_ticket, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (ticket_base) *ticket_base = c->ticket_base;
+    if (epoch) *epoch = c->wide_epoch;
+    if (seam_bytes) *seam_bytes = c->d_seam_bytes;
+    return MVHP_SUCCESS;
+}
+
 MVHP_EXPORT int mvhp_plan_launch(const mvhp_ctx_t *c, const mvhp_plan_device_t *d, const mvhp_stream_params_t *p, int n_frames,
                                  int *layout, int *waves)
 {

@@ -174,6 +174,10 @@ def lib():
     L.mvhp_sync_check.argtypes = [vp, vp]
     L.mvhp_last_launch_info.restype = i32
     L.mvhp_last_launch_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.mvhp_debug_set_wide_state.restype = i32
+    L.mvhp_debug_set_wide_state.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.mvhp_debug_get_wide_state.restype = i32
+    L.mvhp_debug_get_wide_state.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(sz)]
     L.mvhp_plan_launch.restype = i32
     L.mvhp_plan_launch.argtypes = [vp, C.POINTER(PlanDevice), pp, i32, C.POINTER(i32), C.POINTER(i32)]
     pg, u32 = C.POINTER(OutputGeometry), C.c_uint32
@@ -294,6 +298,20 @@ class HotPath:
     def sync_check(self, stream=None):
         if self._L.mvhp_sync_check(self._h, stream) != SUCCESS:
             raise _err(self._L, "mvhp_sync_check")
+
+    def set_wide_state(self, ticket, epoch):
+        """test hook (mvhp_debug_set_wide_state): the ticket counter of the banded forms, on the device and in the host's
+        bookkeeping, and the epoch tag of the last banded launch; waits for every launch issued on the context first"""
+        if self._L.mvhp_debug_set_wide_state(self._h, int(ticket), int(epoch)) != SUCCESS:
+            raise _err(self._L, "mvhp_debug_set_wide_state")
+
+    def get_wide_state(self):
+        """test hook (mvhp_debug_get_wide_state): (ticket counter on the device, the host's mirror of it, epoch tag of the
+        last banded launch, bytes of the seam buffer), once every launch issued on the context has run"""
+        dev, base, epoch, seam = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_size_t()
+        if self._L.mvhp_debug_get_wide_state(self._h, C.byref(dev), C.byref(base), C.byref(epoch), C.byref(seam)) != SUCCESS:
+            raise _err(self._L, "mvhp_debug_get_wide_state")
+        return dev.value, base.value, epoch.value, seam.value
 
     def plan_launch(self, params, n_frames):
         """(layout name, waves per workgroup) the next reconstruction launch of n_frames pictures would use on this context"""

@@ -217,6 +217,8 @@ def test_bookkeeping_across_launches(torch_cuda):
                     for f in range(nn):
                         assert np.array_equal(yuv[f], rf[f % 6][0]), (it, nn, f)
                 pending = []
+        device_ticket, ticket_base, _, _ = hot.get_wide_state()   # one ticket per workgroup of every launch
+        assert device_ticket == ticket_base, (device_ticket, ticket_base)
     finally:
         hot.close()
     torch.cuda.empty_cache()
