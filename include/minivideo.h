@@ -22,6 +22,11 @@
  *     alike.  A malformed MINIVIDEO_THUMBNAIL ("abc", "0x10", "320", a side below 2) is not ignored: minivideo_decode()
  *     returns FAILURE with a message before any device work.  A picture whose crop leaves nothing is skipped like a picture
  *     that does not decode;
+ *   - PICTURE_JPG is written as PNG, as a reference built without libjpeg does (export.c:644-690).  Opt-in, outside the
+ *     reference's behaviour and independent of the switches above: with MINIVIDEO_JPEG=1 PICTURE_JPG writes <name>[_k].jpg,
+ *     baseline JFIF files coded on the GPU from the 4:2:0 planes as export.c:341-430 does with libjpeg (2x2 / 1x1 / 1x1
+ *     sampling, no colour conversion), at picture_quality (clamped to 1 ... 100; otherwise this argument is unused), of the
+ *     coded size or of the size MINIVIDEO_CROP / MINIVIDEO_THUMBNAIL ask for.  The other formats are not affected;
  *   - H.264 IDR pictures only, from Annex-B elementary streams (.264/.h264 or a
  *     file starting with an SPS start code) or from the first H.264 video track
  *     of an MP4/MOV file (demuxer/mp4/mp4.c:1950 mp4_fileParse -> sync samples).

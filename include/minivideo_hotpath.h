@@ -287,6 +287,50 @@ MVHP_EXPORT size_t mvhp_geometry_rgb_bytes(const mvhp_output_geometry_t *g);
 MVHP_EXPORT int    mvhp_resample_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
                                      const uint8_t *d_yuv_coded, int n, uint8_t *d_yuv_out, uint8_t *d_rgb_out, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * JPEG output (opt-in; DESIGN.md 3 "JPEG output"): baseline sequential JFIF files made on the device from planar pictures, the
+ * planes taken as they are (Y 2x2, Cb and Cr 1x1, no colour conversion), as the reference's writer does with libjpeg
+ * (export.c:341-430).  The stream format is fixed -- SOI, APP0 "JFIF" 1.01, one DQT (tables 0 and 1), SOF0, four DHT (the
+ * Annex K.3 tables), DRI, SOS, entropy-coded data with RSTm, EOI -- and the transform is integer-only, so the bytes are a
+ * function of the samples, the quality and the restart interval alone (tests/jpeg_ref.py restates them).
+ * ------------------------------------------------------------------------- */
+typedef struct mvhp_jpeg_params {
+    int32_t  quality;        /* IJG quality, clamped to 1 .. 100: Annex K.1 / K.2 scaled by 5000 / q below 50, else 200 - 2 q   */
+    uint32_t restart_mcus;   /* MCUs (16x16 luma) per restart interval, 1 .. 65535; 0 = one MCU row                            */
+    uint32_t reserved;       /* 0.  Measurements only: MVHP_JPEG_STAGE_* bits run just those stages of a call made before with
+                                the same arguments (its scratch buffer holds what they need).  The write stage checks every
+                                table entry against cap_bytes again, so a stale table cannot send a store outside the blob  */
+} mvhp_jpeg_params_t;
+#define MVHP_JPEG_STAGE_DCT   1u   /* forward DCT + quantisation into the context's scratch buffer                           */
+#define MVHP_JPEG_STAGE_COUNT 2u   /* count pass + the scans: writes the table                                              */
+#define MVHP_JPEG_STAGE_WRITE 4u   /* write pass + headers: writes the blob                                                 */
+
+#define MVHP_JPEG_OK      0u
+#define MVHP_JPEG_TOO_BIG 1u       /* the picture did not fit into what was left of the blob: length 0, nothing written     */
+typedef struct mvhp_jpeg_entry {
+    uint64_t offset;         /* of the picture's file in the blob, a multiple of 16                                          */
+    uint32_t length;         /* bytes of the file                                                                            */
+    uint32_t status;         /* MVHP_JPEG_*                                                                                  */
+} mvhp_jpeg_entry_t;
+
+#define MVHP_JPEG_HEADER_BYTES 625
+/* Bytes of a file before its entropy-coded data (every file of this encoder: the segments above have fixed sizes). */
+MVHP_EXPORT size_t mvhp_jpeg_header_bytes(void);
+/* The two quantisation tables of `quality`, luma then chroma, each in row-major order (the files carry them in zigzag
+ * order).  A host function: needs no device. */
+MVHP_EXPORT int    mvhp_jpeg_quant_tables(int quality, uint8_t out[128]);
+/* n pictures of geometry g (d_yuv: n * mvhp_geometry_yuv_bytes(g), planar Y | Cb | Cr of g->out_w x g->out_h -- coded-size
+ * planes with a geometry of the coded size, or what mvhp_resample_dev delivered; only out_w / out_h are read) -> n JPEG files in
+ * d_blob (16-byte aligned, cap_bytes long) and d_table (n entries, 8-byte aligned).  Pictures are placed in order, each at the
+ * next multiple of 16; a picture whose file would pass cap_bytes is marked MVHP_JPEG_TOO_BIG, takes no room, and those behind
+ * it that fit are placed as if it were not there.  No byte at or beyond cap_bytes is written, nor any between a file's end and
+ * the next file's start.  Pictures of more than 2^28 luma samples are refused (MVHP_UNSUPPORTED): lengths are 32-bit, and a
+ * baseline file is at most 6.5 x its raw picture (26 bits of code and value per level, every byte stuffed).  Asynchronous on `stream` (NULL = the context's own); the intermediate data lives in a scratch buffer
+ * of the context (136 bytes per 8x8 block), so two encodes of one context run one after the other, whatever their streams. */
+MVHP_EXPORT int    mvhp_jpeg_encode_dev(mvhp_ctx_t *ctx, const mvhp_output_geometry_t *g, const mvhp_jpeg_params_t *params,
+                                        const uint8_t *d_yuv, int n, uint8_t *d_blob, size_t cap_bytes,
+                                        mvhp_jpeg_entry_t *d_table, void *stream);
+
 /* Page-locked host memory for the host-buffer entry points (H2D / D2H at full PCIe rate). */
 MVHP_EXPORT void *mvhp_host_alloc(size_t bytes);
 MVHP_EXPORT void  mvhp_host_free(void *p);
@@ -440,6 +484,16 @@ MVHP_EXPORT void mvhp_engine_destroy(mvhp_engine_t *e);
  * are still reconstructed on the device -- RGB is made from them -- but not downloaded: the sink gets yuv = NULL). */
 #define MVHP_OUT_RGB      1
 #define MVHP_OUT_RGB_ONLY 3
+/* mvhp_engine_decode_ex only (opt-in; "JPEG output" above): neither planes nor RGB are downloaded; every picture is coded on the
+ * device by mvhp_jpeg_encode_dev behind the reconstruction (and the deblocking filter and the geometry pass, where the stream
+ * and the request ask for them), and only the files come back.  The sink gets yuv = NULL, rgb = the picture's JPEG file and
+ * g->reserved[0] = its length in bytes.  The encoder's parameters travel in mvhp_output_request_t::reserved: bits 0-7 the
+ * quality (0 = 75, above 100 = 100), bits 8-23 restart_mcus (0 = one MCU row); a request with flags 0 still means pictures of the
+ * coded size.  A batch's blob has room for n x mvhp_geometry_yuv_bytes(g): a picture whose file does not fit into it (larger
+ * than the raw picture: of no use) reaches the sink as a failed picture, and decoding goes on.  d2h_bytes counts the table
+ * entries (16 bytes per picture) and the files' bytes. */
+#define MVHP_OUT_JPEG     4
+#define MVHP_JPEG_REQUEST(quality, restart_mcus) (((uint32_t)(quality) & 0xffu) | (((uint32_t)(restart_mcus) & 0xffffu) << 8))
 /* Decode the pictures order[0..n_order) of `s` (IDR indices) until `wanted` of them have been accepted by the sink
  * (the reference stops after picture_number IDRs, h264.c:173-179: no more pictures than needed are entropy-decoded).
  * sink may be NULL (every reconstructed picture counts as accepted).  Returns MVHP_SUCCESS when `wanted` pictures

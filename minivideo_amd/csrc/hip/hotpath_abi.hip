@@ -78,6 +78,12 @@ struct mvhp_ctx {
     size_t       d_yuv_bytes;
     uint8_t     *d_rgb;
     size_t       d_rgb_bytes;
+    // JPEG encoder (jpeg_encode.hip): levels, non-zero maps and interval lengths of one batch.  One per context: an encode on
+    // another stream waits for the previous one.
+    void        *d_jpeg;
+    size_t       d_jpeg_bytes;
+    hipEvent_t   jpeg_done;
+    hipStream_t  jpeg_stream;
 };
 
 static hipStream_t stream_of(const mvhp_ctx *c, void *stream) { return stream ? (hipStream_t)stream : c->stream; }
@@ -158,6 +164,8 @@ MVHP_EXPORT void mvhp_destroy(mvhp_ctx_t *c)
     if (c->d_rgb) hipFree(c->d_rgb);
     if (c->d_err) hipFree(c->d_err);
     if (c->d_seam) hipFree(c->d_seam);
+    if (c->d_jpeg) hipFree(c->d_jpeg);
+    if (c->jpeg_done) hipEventDestroy(c->jpeg_done);
     if (c->wide_done) hipEventDestroy(c->wide_done);
     hipStreamDestroy(c->stream);
     delete c;
@@ -436,6 +444,64 @@ static int ensure(void **ptr, size_t *have, size_t need)
     return MVHP_SUCCESS;
 }
 
+MVHP_EXPORT size_t mvhp_jpeg_header_bytes(void) { return MVHP_JPEG_HEADER_BYTES; }
+
+MVHP_EXPORT int mvhp_jpeg_quant_tables(int quality, uint8_t out[128])
+{
+    if (!out) return MVHP_FAILURE;
+    mvhp::jpeg_quant_tables(quality, out);
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT int mvhp_jpeg_encode_dev(mvhp_ctx_t *c, const mvhp_output_geometry_t *g, const mvhp_jpeg_params_t *jp,
+                                     const uint8_t *d_yuv, int n, uint8_t *d_blob, size_t cap_bytes, mvhp_jpeg_entry_t *d_table,
+                                     void *stream)
+{
+    if (!c || !g || !jp || !d_yuv || n <= 0 || !d_blob || ((uintptr_t)d_blob & 15) || !d_table || ((uintptr_t)d_table & 7) ||
+        (jp->reserved & ~7u)) {
+        set_err("mvhp_jpeg_encode_dev: invalid argument");
+        return MVHP_FAILURE;
+    }
+    if (((g->out_w | g->out_h) & 1u) || g->out_w < 2 || g->out_h < 2 || g->out_w > 65534 || g->out_h > 65534) {
+        set_err("mvhp_jpeg_encode_dev: pictures of %u x %u cannot be coded (even sides of 2 .. 65534)", g->out_w, g->out_h);
+        return MVHP_FAILURE;
+    }
+    if ((uint64_t)g->out_w * g->out_h > ((uint64_t)1 << 28)) {   // lengths are 32-bit: a file is at most 6.5 x its raw picture
+        set_err("mvhp_jpeg_encode_dev: pictures of %u x %u are too large (at most 2^28 samples of luma)", g->out_w, g->out_h);
+        return MVHP_UNSUPPORTED;
+    }
+    mvhp::JpegArgs a;
+    a.yuv = d_yuv;
+    a.n = n;
+    a.w = (int)g->out_w;
+    a.h = (int)g->out_h;
+    a.quality = jp->quality < 1 ? 1 : jp->quality > 100 ? 100 : jp->quality;
+    a.restart = jp->restart_mcus ? (int)jp->restart_mcus : (a.w + 15) / 16;
+    if (jp->restart_mcus > 65535) {
+        set_err("mvhp_jpeg_encode_dev: restart interval of %u MCUs (1 .. 65535)", jp->restart_mcus);
+        return MVHP_FAILURE;
+    }
+    a.stages = jp->reserved ? (int)jp->reserved : (int)(MVHP_JPEG_STAGE_DCT | MVHP_JPEG_STAGE_COUNT | MVHP_JPEG_STAGE_WRITE);
+    a.blob = d_blob;
+    a.cap = cap_bytes;
+    a.table = d_table;
+    HIP_TRY(hipSetDevice(c->device));
+    const hipStream_t st = stream_of(c, stream);
+    const size_t need = mvhp::jpeg_scratch_bytes(a);
+    if (jp->reserved && c->d_jpeg_bytes < need) {
+        set_err("mvhp_jpeg_encode_dev: single stages need a whole call with the same arguments before them");
+        return MVHP_FAILURE;
+    }
+    if (!c->jpeg_done) HIP_TRY(hipEventCreateWithFlags(&c->jpeg_done, hipEventDisableTiming));
+    if (ensure(&c->d_jpeg, &c->d_jpeg_bytes, need) != MVHP_SUCCESS) return MVHP_FAILURE;   // (hipFree waits for the device)
+    if (c->jpeg_stream && c->jpeg_stream != st) HIP_TRY(hipStreamWaitEvent(st, c->jpeg_done, 0));
+    a.scratch = (uint8_t *)c->d_jpeg;
+    HIP_TRY(mvhp::launch_jpeg_encode(a, st));
+    HIP_TRY(hipEventRecord(c->jpeg_done, st));
+    c->jpeg_stream = st;
+    return MVHP_SUCCESS;
+}
+
 MVHP_EXPORT int mvhp_recon_batch_host(mvhp_ctx_t *c, const mvhp_stream_params_t *p, const void *h_packed,
                                       int n_frames, uint8_t *h_yuv, uint8_t *h_rgb)
 {
@@ -655,9 +721,18 @@ int eng_d2h(DevCtx *d, int n, void *const *dst, const void *const *src, const si
 
 // g == NULL: planes (+ RGB into d_rgb) of the coded size.  Otherwise: planes of the coded size into d_yuv without the fused
 // colour epilogue, the deblocking filter when p asks for it, then the output-geometry pass into out_yuv / out_rgb.
+// j != NULL: planes only, as for a geometry, and the JPEG encoder behind them (on out_yuv when g is given, else on d_yuv).
+struct JpegOut {
+    const mvhp_jpeg_params_t     *params;
+    const mvhp_output_geometry_t *geom;    // of the pictures that are coded
+    uint8_t                      *blob;
+    size_t                        cap;
+    mvhp_jpeg_entry_t            *table;
+};
+
 int eng_recon_impl(DevCtx *d, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const void *d_compact, size_t stride,
                    void *d_packed, int n, uint8_t *d_yuv, uint8_t *d_rgb, uint8_t *out_yuv, uint8_t *out_rgb, float *ms, int *layout,
-                   int *waves, std::string &err)
+                   int *waves, std::string &err, const JpegOut *j = nullptr)
 {
     mvhp_ctx *c = d->c;
     if (!params_ok(p) || !d_compact || !d_packed || !d_yuv || n <= 0) { err = "reconstruction: invalid argument"; return MVHP_FAILURE; }
@@ -665,11 +740,15 @@ int eng_recon_impl(DevCtx *d, const mvhp_stream_params_t *p, const mvhp_output_g
     ENG_TRY(hipEventRecord(d->ev[2], c->stream));
     if (mvhp_expand_compact_dev(c, p, d_compact, stride, n, d_packed, c->stream) != MVHP_SUCCESS) { err = mvhp_last_error(); return MVHP_FAILURE; }
     const bool deblock = (p->flags & MVHP_PARAM_DEBLOCK) != 0;
-    int rc = g ? launch_all(c, p, d_packed, n, d_yuv, nullptr, c->stream, true, false, deblock)
+    int rc = (g || j) ? launch_all(c, p, d_packed, n, d_yuv, nullptr, c->stream, true, false, deblock)
                : launch_all(c, p, d_packed, n, d_yuv, d_rgb, c->stream, true, true, deblock);
     if (rc != MVHP_SUCCESS) { err = mvhp_last_error(); return rc; }
     if (g) {
         rc = mvhp_resample_dev(c, p, g, d_yuv, n, out_yuv, out_rgb, c->stream);
+        if (rc != MVHP_SUCCESS) { err = mvhp_last_error(); return rc; }
+    }
+    if (j) {
+        rc = mvhp_jpeg_encode_dev(c, j->geom, j->params, g ? out_yuv : d_yuv, n, j->blob, j->cap, j->table, c->stream);
         if (rc != MVHP_SUCCESS) { err = mvhp_last_error(); return rc; }
     }
     ENG_TRY(hipEventRecord(d->ev[3], c->stream));
@@ -699,6 +778,17 @@ int eng_recon_geometry(DevCtx *d, const mvhp_stream_params_t *p, const mvhp_outp
 {
     if (!g) { err = "reconstruction: no output geometry"; return MVHP_FAILURE; }
     return eng_recon_impl(d, p, g, d_compact, stride, d_packed, n, d_yuv_coded, nullptr, d_yuv_out, d_rgb_out, ms, layout, waves, err);
+}
+
+int eng_recon_jpeg(DevCtx *d, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, int resample,
+                   const mvhp_jpeg_params_t *jp, const void *d_compact, size_t stride, void *d_packed, int n, uint8_t *d_yuv_coded,
+                   uint8_t *d_yuv_out, uint8_t *d_blob, size_t cap_bytes, mvhp_jpeg_entry_t *d_table, float *ms, int *layout,
+                   int *waves, std::string &err)
+{
+    if (!g || !jp || !d_blob || !d_table || (resample && !d_yuv_out)) { err = "reconstruction: invalid JPEG output"; return MVHP_FAILURE; }
+    const JpegOut j = {jp, g, d_blob, cap_bytes, d_table};
+    return eng_recon_impl(d, p, resample ? g : nullptr, d_compact, stride, d_packed, n, d_yuv_coded, nullptr, d_yuv_out, nullptr, ms,
+                          layout, waves, err, &j);
 }
 
 // the engine's batch buffers from one placed arena (MINIVIDEO_PLACED=1): records / planes / RGB of a batch in three groups of
@@ -738,6 +828,7 @@ void eng_placed_free(DevCtx *d, void *arena)
 const mvengine::DeviceApi g_hip_api = {
     mvhp_device_count, mvhp_host_alloc, mvhp_host_free, eng_ctx_create, eng_ctx_destroy, eng_dev_alloc, eng_dev_free,
     eng_dev_free_bytes, eng_h2d, eng_d2h, eng_recon, eng_placed_alloc, eng_placed_free, eng_recon_geometry,
+    eng_recon_jpeg,
 };
 
 } // namespace

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "minivideo_hotpath.h"
+
 namespace mvhp {
 
 struct ReconArgs {
@@ -103,5 +105,22 @@ size_t     resample_lds_bytes(int cw, int ow, int band);
 hipError_t launch_resample(const ResampleArgs &a, hipStream_t stream);
 // crop only (ow == cw, oh == ch) as a copy from global memory to global memory (crop_copy.hip): the same bytes, no LDS, any width
 hipError_t launch_crop_copy(const ResampleArgs &a, hipStream_t stream);
+
+// baseline JPEG from planar pictures (jpeg_encode.hip): DCT + quantisation, count, scans, write, headers
+struct JpegArgs {
+    const uint8_t     *yuv;      // n pictures, planar Y | Cb | Cr of w x h
+    int                n, w, h;  // w, h even, 2 .. 65534
+    int                quality;  // clamped to 1 .. 100
+    int                restart;  // MCUs per restart interval, 1 .. 65535
+    int                stages;   // MVHP_JPEG_STAGE_*
+    uint8_t           *blob;     // 16-byte aligned
+    size_t             cap;
+    mvhp_jpeg_entry_t *table;    // n entries
+    uint8_t           *scratch;  // jpeg_scratch_bytes(), 16-byte aligned
+};
+size_t     jpeg_scratch_bytes(const JpegArgs &a);
+hipError_t launch_jpeg_encode(const JpegArgs &a, hipStream_t stream);
+void       jpeg_quant_tables(int quality, uint8_t out[128]);
+void       jpeg_header(int w, int h, int quality, int restart, uint8_t out[MVHP_JPEG_HEADER_BYTES]);
 
 } // namespace mvhp

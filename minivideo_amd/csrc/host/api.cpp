@@ -293,7 +293,7 @@ struct ExportSink {
     // File writers (round 3): one picture's write to the page cache is a 3-6 MB copy, 0.5 ms -- on the calling thread that
     // capped minivideo_decode at 2000 pictures/s while the pipeline delivers 3300.  The sink keeps the picture (verdict 2),
     // a small pool writes it and gives it back.  MINIVIDEO_WRITERS=0: write on the calling thread as before.
-    struct Job { int seq; std::string name; int W, H; const uint8_t *yuv, *rgb; };
+    struct Job { int seq; std::string name; int W, H; const uint8_t *yuv, *rgb; size_t file_bytes; };
     mvhp_engine_t *eng = nullptr;
     std::vector<std::thread> pool;
     std::mutex mu;
@@ -306,8 +306,15 @@ struct ExportSink {
     std::atomic<int> written{0}, write_errors{0};
     bool stopped_by_write_error = false;
 
-    int write_one(const std::string &name, int W, int H, const uint8_t *yuv, const uint8_t *rgb) const
+    // file_bytes: PICTURE_JPG under MINIVIDEO_JPEG=1 only -- `rgb` then is the finished file (made on the device)
+    int write_one(const std::string &name, int W, int H, const uint8_t *yuv, const uint8_t *rgb, size_t file_bytes) const
     {
+        if (fmt == PICTURE_JPG) {
+            FILE *f = fopen(name.c_str(), "wb");
+            if (!f) return 0;
+            const bool ok = fwrite(rgb, 1, file_bytes, f) == file_bytes;
+            return (fclose(f) == 0 && ok) ? 1 : 0;
+        }
         if (fmt == PICTURE_PNG) return mvexport::write_png(name, rgb, W, H);
         if (fmt == PICTURE_BMP) return mvexport::write_bmp(name, rgb, W, H);
         if (fmt == PICTURE_TGA) return mvexport::write_tga(name, rgb, W, H);
@@ -342,7 +349,7 @@ struct ExportSink {
                 j = std::move(jobs.front());
                 jobs.pop_front();
             }
-            if (write_one(j.name, j.W, j.H, j.yuv, j.rgb)) written++;
+            if (write_one(j.name, j.W, j.H, j.yuv, j.rgb, j.file_bytes)) written++;
             else { log_err("Unable to write '%s'", j.name.c_str()); write_errors++; }
             mvhp_engine_release_picture(eng, j.seq);
             {
@@ -370,6 +377,7 @@ struct ExportSink {
         name += ".";
         name += x.ext;
         const int W = (int)g->out_w, H = (int)g->out_h;   // the coded size unless MINIVIDEO_CROP / MINIVIDEO_THUMBNAIL ask for less
+        const size_t file_bytes = x.fmt == PICTURE_JPG ? g->reserved[0] : 0;   // (MVHP_OUT_JPEG: the length of the file in `rgb`)
         if (!x.pool.empty()) {
             // Writers run behind the pipeline, so a write that fails is only known later: no further picture is decoded in
             // its place (the synchronous path below does that).  Once one has failed -- a full disk does not get better --
@@ -379,13 +387,13 @@ struct ExportSink {
                 std::unique_lock<std::mutex> l(x.mu);
                 x.cv_room.wait(l, [&] { return x.in_flight < x.max_jobs; });
                 x.in_flight++;
-                x.jobs.push_back(Job{seq, std::move(name), W, H, yuv, rgb});
+                x.jobs.push_back(Job{seq, std::move(name), W, H, yuv, rgb, file_bytes});
             }
             x.cv_job.notify_one();
             x.exported++;
             return 2;
         }
-        if (!x.write_one(name, W, H, yuv, rgb)) {
+        if (!x.write_one(name, W, H, yuv, rgb, file_bytes)) {
             log_err("Unable to write '%s'", name.c_str());
             x.errors++;
             return 0;
@@ -509,7 +517,6 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
                                       const int picture_extractionmode)
 {
     (void)output_directory; // accepted and ignored, like the reference (h264.c:65)
-    (void)picture_quality;
     if (!m) { log_err("Unable to start decoding because of an empty MediaFile_t structure! Parsing failed?"); return FAILURE; }
     BitstreamMap_t *map = m->tracks_video[0];
     if (!map || map->stream_type != stream_VIDEO) { log_err("No video track to decode"); return FAILURE; }
@@ -567,10 +574,14 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     if (picture_extractionmode != PICTURE_UNFILTERED && (int)order.size() < wanted) wanted = (int)order.size();
 
     // export.c:644-690: format fallbacks of a build with stb_image_write only (ENABLE_JPEG = ENABLE_PNG = 0)
+    // opt-in (MINIVIDEO_JPEG=1, outside the parity contract): PICTURE_JPG is written as JPEG, coded on the device from the planes as
+    // export.c:341-430 does with libjpeg (jpeg_set_quality(picture_quality), 2x2 / 1x1 / 1x1, no colour conversion)
+    const bool jpeg = picture_format == PICTURE_JPG && getenv("MINIVIDEO_JPEG") && atoi(getenv("MINIVIDEO_JPEG")) != 0;
     int fmt = picture_format;
-    if (fmt == PICTURE_JPG) fmt = PICTURE_PNG;
+    if (fmt == PICTURE_JPG && !jpeg) fmt = PICTURE_PNG;
     const char *ext = "yuv";
-    if (fmt == PICTURE_PNG) ext = "png";
+    if (fmt == PICTURE_JPG) ext = "jpg";
+    else if (fmt == PICTURE_PNG) ext = "png";
     else if (fmt == PICTURE_BMP) ext = "bmp";
     else if (fmt == PICTURE_TGA) ext = "tga";
     const bool want_rgb = (fmt == PICTURE_PNG || fmt == PICTURE_BMP || fmt == PICTURE_TGA);
@@ -601,8 +612,10 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     mvhp_decode_stats_t st;
     // decodes in order until `wanted` pictures have been written (h264.c:173-179) or 64 errors in a row (h264.c:181-187)
     // RGB formats are written from the RGB picture alone: the planes stay on the device
-    (void)mvhp_engine_decode_ex(eng, &s, order.data(), (int)order.size(), wanted, want_rgb ? MVHP_OUT_RGB_ONLY : 0,
-                                req.flags ? &req : nullptr, ExportSink::call, &sink, &st);
+    // JPEG files come back finished: only their bytes are downloaded and written
+    if (jpeg) req.reserved = MVHP_JPEG_REQUEST(std::min(100, std::max(1, picture_quality)), 0);
+    (void)mvhp_engine_decode_ex(eng, &s, order.data(), (int)order.size(), wanted, jpeg ? MVHP_OUT_JPEG : want_rgb ? MVHP_OUT_RGB_ONLY : 0,
+                                (req.flags || jpeg) ? &req : nullptr, ExportSink::call, &sink, &st);
     sink.finish();   // (every kept picture is back: mvhp_engine_decode waits for that)
     if (getenv("MINIVIDEO_STATS")) {
         fprintf(stderr, "[minivideo] decode call: reading the file %.3f s, indexing %.3f s, engine up after %.3f s (its thread took "

@@ -112,7 +112,8 @@ struct InChunk {
 };
 
 struct OutChunk {
-    Pinned yuv, rgb;
+    Pinned yuv, rgb;         // (MVHP_OUT_JPEG: rgb holds the files of the chunk's pictures, tab their table entries)
+    Pinned tab;
     int refs = 0;            // pictures handed to the sink queue and not yet consumed
 };
 
@@ -140,6 +141,9 @@ struct DevBuf {
     // allocations always, also beside a placed arena: they are the small side of such a batch.
     uint8_t *out_yuv = nullptr, *out_rgb = nullptr;
     size_t out_yuv_cap = 0, out_rgb_cap = 0;
+    // MVHP_OUT_JPEG: the encoder's blob (n x the raw picture) and table of a batch
+    uint8_t *jpeg_blob = nullptr, *jpeg_tab = nullptr;
+    size_t jpeg_blob_cap = 0, jpeg_tab_cap = 0;
     void leave_arena()          // the four arena pieces are forgotten (they go with the arena); the output buffers stay
     {
         compact = packed = nullptr;
@@ -266,6 +270,8 @@ private:
     const int *order_ = nullptr;
     int n_order_ = 0, wanted_ = 0;
     bool want_rgb_ = false, want_yuv_ = true;   // which outputs are downloaded (the planes are always reconstructed)
+    bool want_jpeg_ = false;                    // MVHP_OUT_JPEG: neither of them; JPEG files made on the device are
+    mvhp_jpeg_params_t jpeg_{};
     mvhp_output_request_t req_{};               // flags 0: pictures of the coded size
     bool stop_ = false;
     bool sink_waiting_ = false;
@@ -297,7 +303,7 @@ private:
 Engine::~Engine()
 {
     for (auto &c : all_in_) api_.host_free(c->buf.p);
-    for (auto &c : all_out_) { api_.host_free(c->yuv.p); api_.host_free(c->rgb.p); }
+    for (auto &c : all_out_) { api_.host_free(c->yuv.p); api_.host_free(c->rgb.p); api_.host_free(c->tab.p); }
     for (Ctx &c : ctx_) {
         if (c.arena) {   // pieces of the arena go with it; a buffer that left the arena is freed below like any other
             for (DevBuf &b : c.bufs) if (b.arena_piece) b.leave_arena();
@@ -310,6 +316,8 @@ Engine::~Engine()
             if (b.rgb) api_.dev_free(c.dev, b.rgb);
             if (b.out_yuv) api_.dev_free(c.dev, b.out_yuv);
             if (b.out_rgb) api_.dev_free(c.dev, b.out_rgb);
+            if (b.jpeg_blob) api_.dev_free(c.dev, b.jpeg_blob);
+            if (b.jpeg_tab) api_.dev_free(c.dev, b.jpeg_tab);
         }
         if (c.dev) api_.ctx_destroy(c.dev);
     }
@@ -412,8 +420,11 @@ int Engine::batch_capacity(const mvhp_stream_params_t &p, const mvhp_output_geom
     // product path reaches the kernel the bench times; the ramp and the taper stay as they are)
     int cap = opts_.batch_pictures > 0 ? opts_.batch_pictures : ((n_order_ >= 4096 * n_ctx) ? 2048 : 1024);
     const size_t per_pic = compact_slot_bytes(p) + mvhp_packed_frame_bytes(&p) + mvhp_yuv_frame_bytes(&p) +
-                           (g ? (want_yuv_ ? mvhp_geometry_yuv_bytes(g) : 0) + (want_rgb_ ? mvhp_geometry_rgb_bytes(g) : 0)
-                              : (want_rgb_ ? mvhp_rgb_frame_bytes(&p) : 0));
+                           (g ? (want_yuv_ || want_jpeg_ ? mvhp_geometry_yuv_bytes(g) : 0) + (want_rgb_ ? mvhp_geometry_rgb_bytes(g) : 0)
+                              : (want_rgb_ ? mvhp_rgb_frame_bytes(&p) : 0)) +
+                           // (the blob, 1 x the planes, and the encoder's scratch in the context, 136 bytes per 8x8 block = 2.125 x the planes
+                           //  padded to whole MCUs: 3.125 x, budgeted as 4.25 x for that padding on small pictures)
+                           (want_jpeg_ ? (g ? mvhp_geometry_yuv_bytes(g) : mvhp_yuv_frame_bytes(&p)) * 17 / 4 : 0);
     size_t budget = ctx_[0].mem_budget;
     for (const Ctx &c : ctx_) budget = std::min(budget, c.mem_budget);
     const int mem_cap = (int)std::min<size_t>(1 << 20, std::max<size_t>(1, budget / std::max<size_t>(1, per_pic)));
@@ -531,7 +542,7 @@ bool Engine::ensure_devbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
 // change inside a job; these buffers are the small side of a batch)
 bool Engine::ensure_outbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
 {
-    if (!bt.use_geom) return true;
+    if (!bt.use_geom && !want_jpeg_) return true;
     const size_t n = (size_t)bt.capacity;
     auto need = [&](uint8_t **ptr, size_t *cap, size_t bytes) {
         if (*cap >= bytes) return true;
@@ -546,7 +557,13 @@ bool Engine::ensure_outbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
         }
         return *ptr != nullptr;
     };
-    if ((want_yuv_ && !need(&b.out_yuv, &b.out_yuv_cap, n * mvhp_geometry_yuv_bytes(&bt.geom))) ||
+    if (want_jpeg_ && (!need(&b.jpeg_blob, &b.jpeg_blob_cap, n * mvhp_geometry_yuv_bytes(&bt.geom)) ||
+                       !need(&b.jpeg_tab, &b.jpeg_tab_cap, n * sizeof(mvhp_jpeg_entry_t)))) {
+        err = "out of device memory for the JPEG files of a batch of " + std::to_string(bt.capacity);
+        return false;
+    }
+    if (!bt.use_geom) return true;
+    if (((want_yuv_ || want_jpeg_) && !need(&b.out_yuv, &b.out_yuv_cap, n * mvhp_geometry_yuv_bytes(&bt.geom))) ||
         (want_rgb_ && !need(&b.out_rgb, &b.out_rgb_cap, n * mvhp_geometry_rgb_bytes(&bt.geom)))) {
         err = "out of device memory for the output pictures of a batch of " + std::to_string(bt.capacity);
         return false;
@@ -917,6 +934,13 @@ void Engine::launcher(int k)
         int rc = MVHP_SUCCESS;
         const double t_call = now_s();
         if (inject) { rc = MVHP_FAILURE; err = "injected failure (test hook)"; }
+        else if (want_jpeg_ && !api_.recon_jpeg) { rc = MVHP_FAILURE; err = "this device table has no JPEG operation"; }
+        else if (want_jpeg_)
+            rc = api_.recon_jpeg(cx.dev, &b->params, &b->geom, b->use_geom ? 1 : 0, &jpeg_, b->buf->compact,
+                                 compact_slot_bytes(b->params), b->buf->packed, b->total, b->buf->yuv,
+                                 b->use_geom ? b->buf->out_yuv : nullptr, b->buf->jpeg_blob,
+                                 (size_t)b->total * mvhp_geometry_yuv_bytes(&b->geom), (mvhp_jpeg_entry_t *)b->buf->jpeg_tab, &ms,
+                                 &layout, &waves, err);
         else if (!b->use_geom)
             rc = api_.recon(cx.dev, &b->params, b->buf->compact, compact_slot_bytes(b->params), b->buf->packed, b->total,
                             b->buf->yuv, want_rgb_ ? b->buf->rgb : nullptr, &ms, &layout, &waves, err);
@@ -1007,6 +1031,74 @@ void Engine::downloader(int k)
             }
             std::string err;
             float ms = 0.f, ms2 = 0.f;
+            if (want_jpeg_) {   // the table rows of the chunk's pictures, then exactly the bytes they name, one piece per file
+                const mvhp_jpeg_entry_t *tab = nullptr;
+                size_t base = 0, span = 0, moved = (size_t)n * sizeof(mvhp_jpeg_entry_t);
+                bool ok = grow(oc->tab, (size_t)C * sizeof(mvhp_jpeg_entry_t));
+                if (!ok) err = "out of page-locked host memory";
+                if (ok) {
+                    void *dst = oc->tab.p;
+                    const void *src = b->buf->jpeg_tab + (size_t)g * sizeof(mvhp_jpeg_entry_t);
+                    ok = api_.d2h(cx.dev, 1, &dst, &src, &moved, &ms, err) == MVHP_SUCCESS;
+                    tab = (const mvhp_jpeg_entry_t *)oc->tab.p;
+                }
+                const size_t blob_cap = (size_t)b->total * mvhp_geometry_yuv_bytes(&b->geom);
+                if (ok) {
+                    base = (size_t)tab[0].offset;
+                    for (int i = 0; i < n && ok; i++) {
+                        if (tab[i].status != MVHP_JPEG_OK) continue;
+                        if (tab[i].offset < base || tab[i].offset > blob_cap || tab[i].length > blob_cap - tab[i].offset) {
+                            ok = false;
+                            err = "the JPEG table names bytes outside the blob";
+                        }
+                        span = std::max(span, (size_t)(tab[i].offset - base) + tab[i].length);
+                    }
+                }
+                if (ok && span && !grow(oc->rgb, span)) { ok = false; err = "out of page-locked host memory"; }
+                if (ok && span) {
+                    std::vector<void *> dst;
+                    std::vector<const void *> src;
+                    std::vector<size_t> nb;
+                    for (int i = 0; i < n; i++) {
+                        if (tab[i].status != MVHP_JPEG_OK) continue;
+                        dst.push_back(oc->rgb.p + (tab[i].offset - base));
+                        src.push_back(b->buf->jpeg_blob + tab[i].offset);
+                        nb.push_back(tab[i].length);
+                        moved += tab[i].length;
+                    }
+                    ok = api_.d2h(cx.dev, (int)dst.size(), dst.data(), src.data(), nb.data(), &ms2, err) == MVHP_SUCCESS;
+                }
+                {
+                    std::lock_guard<std::mutex> l(mu_);
+                    if (ok) {
+                        st_.d2h_s += (ms + ms2) * 1e-3;
+                        st_.d2h_bytes += moved;
+                        oc->refs = 0;
+                        for (int i = 0; i < n; i++) {
+                            PicResult &r = results_[(size_t)b->seqs[(size_t)(g + i)]];
+                            if (!r.parsed_ok || r.ready) continue;
+                            if (tab[i].status == MVHP_JPEG_OK) {
+                                r.rc = MVHP_SUCCESS;
+                                r.oc = oc;
+                                r.rgb = oc->rgb.p + (tab[i].offset - base);
+                                r.geom.reserved[0] = tab[i].length;
+                                oc->refs++;
+                            } else {   // a JPEG larger than the raw picture is of no use: the picture fails, decoding goes on
+                                r.rc = MVHP_FAILURE;
+                                r.err = "the JPEG file does not fit into the room of the raw picture";
+                            }
+                            r.yuv = nullptr;
+                            r.ready = true;
+                        }
+                        if (oc->refs == 0) put_out(oc);
+                    } else {
+                        put_out(oc);
+                        fail = err;
+                    }
+                }
+                cv_.notify_all();
+                continue;
+            }
             bool ok = (!want_yuv_ || grow(oc->yuv, (size_t)C * yb)) && (!want_rgb_ || grow(oc->rgb, (size_t)C * rb));
             if (!ok) err = "out of page-locked host memory";
             if (ok) {
@@ -1066,6 +1158,10 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         err = "malformed output request (box sides must be at least 2)";
         return MVHP_FAILURE;
     }
+    if ((out_mask & MVHP_OUT_JPEG) && sink) {
+        err = "MVHP_OUT_JPEG needs mvhp_engine_decode_ex: its sink gets the file's length with the geometry";
+        return MVHP_FAILURE;
+    }
     if (!order || n_order <= 0 || wanted <= 0) { err = "nothing to decode"; return MVHP_FAILURE; }
     for (int i = 0; i < n_order; i++)
         if (order[i] < 0 || (size_t)order[i] >= s.idrs.size()) { err = "IDR index out of range"; return MVHP_FAILURE; }
@@ -1074,8 +1170,15 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
     {
         std::lock_guard<std::mutex> l(mu_);
         s_ = &s; order_ = order; n_order_ = n_order; wanted_ = std::min(wanted, n_order);
-        want_rgb_ = (out_mask & 1) != 0;
-        want_yuv_ = !want_rgb_ || (out_mask & 2) == 0;
+        want_jpeg_ = (out_mask & MVHP_OUT_JPEG) != 0;
+        want_rgb_ = !want_jpeg_ && (out_mask & 1) != 0;
+        want_yuv_ = !want_jpeg_ && (!want_rgb_ || (out_mask & 2) == 0);
+        jpeg_ = mvhp_jpeg_params_t{};
+        if (want_jpeg_) {   // mvhp_output_request_t::reserved carries the encoder's parameters
+            const uint32_t rsv = req ? req->reserved : 0;
+            jpeg_.quality = (rsv & 0xffu) ? (int32_t)(rsv & 0xffu) : 75;
+            jpeg_.restart_mcus = (rsv >> 8) & 0xffffu;
+        }
         req_ = req ? *req : mvhp_output_request_t{};
         stop_ = false; sink_waiting_ = false;
         pos_ = issued_ = consumed_ = ok_ = failed_ = 0;

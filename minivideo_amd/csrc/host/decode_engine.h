@@ -50,6 +50,14 @@ struct DeviceApi {
     int    (*recon_geometry)(DevCtx *c, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const void *d_compact,
                              size_t stride, void *d_packed, int n_pictures, uint8_t *d_yuv_coded, uint8_t *d_yuv_out,
                              uint8_t *d_rgb_out, float *ms, int *layout, int *waves, std::string &err);
+    // optional (may be NULL: a call with MVHP_OUT_JPEG then fails), last for the same reason: `recon` planes only into d_yuv_coded,
+    // the deblocking filter when p asks for it, mvhp_resample_dev into d_yuv_out when `resample` (g then differs from the coded
+    // size; otherwise d_yuv_out is NULL), then mvhp_jpeg_encode_dev of the n pictures of geometry g into d_blob (cap_bytes) and
+    // d_table (n entries)
+    int    (*recon_jpeg)(DevCtx *c, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, int resample,
+                         const mvhp_jpeg_params_t *jp, const void *d_compact, size_t stride, void *d_packed, int n_pictures,
+                         uint8_t *d_yuv_coded, uint8_t *d_yuv_out, uint8_t *d_blob, size_t cap_bytes, mvhp_jpeg_entry_t *d_table,
+                         float *ms, int *layout, int *waves, std::string &err);
 };
 
 class Engine;

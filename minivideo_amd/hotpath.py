@@ -51,6 +51,7 @@ class StreamParams(C.Structure):
         return self.mbs * 768
 
 
+OUT_JPEG = 4                                                            # mvhp_engine_decode_ex output kind (MVHP_OUT_JPEG)
 OUTPUT_CROP, OUTPUT_BOX = 1, 2                                          # mvhp_output_request_t flags (MVHP_OUTPUT_*)
 
 
@@ -81,6 +82,33 @@ def output_request(output):
         return OutputRequest(OUTPUT_CROP, 0, 0, 0)
     w, h = output
     return OutputRequest(OUTPUT_CROP | OUTPUT_BOX, int(w), int(h), 0)
+
+
+class JpegParams(C.Structure):
+    """mvhp_jpeg_params_t"""
+    _fields_ = [("quality", C.c_int32), ("restart_mcus", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class JpegEntry(C.Structure):
+    """mvhp_jpeg_entry_t: where a picture's file lies in the blob"""
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("status", C.c_uint32)]
+
+
+JPEG_OK, JPEG_TOO_BIG = 0, 1                                            # mvhp_jpeg_entry_t status (MVHP_JPEG_*)
+JPEG_STAGE_DCT, JPEG_STAGE_COUNT, JPEG_STAGE_WRITE = 1, 2, 4            # measurements only (MVHP_JPEG_STAGE_*)
+JPEG_ENTRY_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u4"), ("status", "<u4")])
+
+
+def jpeg_header_bytes():
+    return int(lib().mvhp_jpeg_header_bytes())
+
+
+def jpeg_quant_tables(quality):
+    """mvhp_jpeg_quant_tables: (2, 64) uint8, luma and chroma, row-major (no device needed)"""
+    out = np.empty(128, dtype=np.uint8)
+    if lib().mvhp_jpeg_quant_tables(int(quality), out.ctypes.data) != SUCCESS:
+        raise MiniVideoError("mvhp_jpeg_quant_tables failed")
+    return out.reshape(2, 64)
 
 
 def geometry(crop_x, crop_y, crop_w, crop_h, out_w=None, out_h=None):
@@ -192,6 +220,12 @@ def lib():
         getattr(L, f).argtypes = [pg]
     L.mvhp_resample_dev.restype = i32
     L.mvhp_resample_dev.argtypes = [vp, pp, pg, vp, i32, vp, vp, vp]
+    L.mvhp_jpeg_header_bytes.restype = sz
+    L.mvhp_jpeg_header_bytes.argtypes = []
+    L.mvhp_jpeg_quant_tables.restype = i32
+    L.mvhp_jpeg_quant_tables.argtypes = [i32, vp]
+    L.mvhp_jpeg_encode_dev.restype = i32
+    L.mvhp_jpeg_encode_dev.argtypes = [vp, pg, C.POINTER(JpegParams), vp, i32, vp, sz, vp, vp]
     L.mvhp_stream_last_error.restype = C.c_char_p
     if hasattr(L, "mvhp_stream_open"):
         L.mvhp_stream_open.restype = i32
@@ -294,6 +328,15 @@ class HotPath:
         rc = self._L.mvhp_resample_dev(self._h, C.byref(params), C.byref(geom), d_yuv_coded, int(n), d_yuv_out, d_rgb_out, stream)
         if rc != SUCCESS:
             raise _err(self._L, "mvhp_resample_dev")
+
+    def jpeg_encode_dev(self, geom, d_yuv, n, d_blob, cap_bytes, d_table, quality=75, restart_mcus=0, stream=None, stages=0):
+        """n pictures of OutputGeometry `geom` (planar, device) -> JPEG files in d_blob (16-byte aligned, cap_bytes) and n
+        JpegEntry records (JPEG_ENTRY_DTYPE) in d_table, both device memory; restart_mcus 0 = one MCU row.  Asynchronous.
+        stages: measurements only (JPEG_STAGE_*), 0 = the whole encode."""
+        jp = JpegParams(int(quality), int(restart_mcus), int(stages))
+        rc = self._L.mvhp_jpeg_encode_dev(self._h, C.byref(geom), C.byref(jp), d_yuv, int(n), d_blob, int(cap_bytes), d_table, stream)
+        if rc != SUCCESS:
+            raise _err(self._L, "mvhp_jpeg_encode_dev")
 
     def sync_check(self, stream=None):
         if self._L.mvhp_sync_check(self._h, stream) != SUCCESS:
@@ -444,30 +487,35 @@ class Engine:
         """gives back a picture whose sink call answered 2 (any thread; the decode call returns when the last one is back)"""
         self._L.mvhp_engine_release_picture(self._h, int(seq))
 
-    def decode(self, stream_handle, order, wanted=None, want_rgb=False, sink=None, output=None):
+    def decode(self, stream_handle, order, wanted=None, want_rgb=False, sink=None, output=None, jpeg=None, restart_mcus=0):
         """sink(seq, idr, rc, err, params, yuv ndarray | None, rgb ndarray | None) -> 1 accept / 0 reject / -1 stop /
         2 accept and keep until release_picture(seq); the arrays are views of page-locked memory valid only during the call
         (or until the release).  Returns (rc, stats dict).
         output (see output_request()): None = pictures of the coded size (mvhp_engine_decode); "crop" or a (w, h) box =
         mvhp_engine_decode_ex, and the sink is called with one more argument after params, the picture's OutputGeometry (a
-        copy): sink(seq, idr, rc, err, params, geometry, yuv, rgb), the arrays sized by it."""
+        copy): sink(seq, idr, rc, err, params, geometry, yuv, rgb), the arrays sized by it.
+        jpeg = a quality (1 .. 100): MVHP_OUT_JPEG -- the pictures (of the coded size, or of `output`) are coded as JPEG on the
+        device and only the files come back: sink(seq, idr, rc, err, params, geometry, None, file bytes as a uint8 array);
+        want_rgb is ignored; restart_mcus 0 = one MCU row."""
         order = (C.c_int * len(order))(*order)
         st = DecodeStats()
         n_wanted = len(order) if wanted is None else wanted
-        if output is not None:
-            req = output_request(output)
+        if output is not None or jpeg is not None:
+            req = output_request(output) or OutputRequest(0, 0, 0, 0)
+            if jpeg is not None:
+                req.reserved = (min(max(int(jpeg), 1), 100) & 0xff) | ((int(restart_mcus) & 0xffff) << 8)
 
             def _cbx(user, seq, idr, rc, err, p, g, yuv, rgb):
                 if sink is None:
                     return 1 if rc == SUCCESS else 0
                 pr, geom = p.contents, OutputGeometry.from_buffer_copy(g.contents)
                 y = np.ctypeslib.as_array(yuv, shape=(geom.yuv_bytes,)) if yuv else None
-                r = np.ctypeslib.as_array(rgb, shape=(geom.rgb_bytes,)) if rgb else None
+                r = np.ctypeslib.as_array(rgb, shape=(geom.reserved[0] if jpeg is not None else geom.rgb_bytes,)) if rgb else None
                 return int(sink(seq, idr, rc, err.decode() if err else "", pr, geom, y, r))
 
             cbx = SINK_EX_T(_cbx) if sink is not None else C.cast(None, SINK_EX_T)
-            rc = self._L.mvhp_engine_decode_ex(self._h, stream_handle, order, len(order), n_wanted, int(want_rgb),
-                                               C.byref(req), cbx, None, C.byref(st))
+            rc = self._L.mvhp_engine_decode_ex(self._h, stream_handle, order, len(order), n_wanted,
+                                               OUT_JPEG if jpeg is not None else int(want_rgb), C.byref(req), cbx, None, C.byref(st))
             return rc, st.as_dict()
 
         def _cb(user, seq, idr, rc, err, p, yuv, rgb):

@@ -155,10 +155,54 @@ int stub_recon_geometry(DevCtx *, const mvhp_stream_params_t *p, const mvhp_outp
     return MVHP_SUCCESS;
 }
 
+// The JPEG operation: the coded planes (and the output planes of a batch with a geometry) are written in full, and every picture
+// gets a "file" whose length depends on its records -- 32 + checksum % (half the raw picture) bytes of 0x3c, the checksum in bytes
+// 0-7, 0x79 last -- at the next multiple of 16 of the blob; a picture whose checksum is a multiple of 5 is reported too big.
+constexpr uint8_t kLastJpeg = 0x79;
+std::atomic<int> g_jpeg_calls{0};
+size_t stub_jpeg_length(uint64_t h, size_t raw) { return 32 + (size_t)(h % (raw / 2)); }
+bool stub_jpeg_too_big(uint64_t h) { return h % 5 == 0; }
+int stub_recon_jpeg(DevCtx *, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, int resample, const mvhp_jpeg_params_t *jp,
+                    const void *d_compact, size_t stride, void *d_packed, int n, uint8_t *d_yuv_coded, uint8_t *d_yuv_out,
+                    uint8_t *d_blob, size_t cap, mvhp_jpeg_entry_t *d_table, float *ms, int *layout, int *waves, std::string &err)
+{
+    g_jpeg_calls++;
+    if (!g || !jp || !d_yuv_coded || !d_blob || !d_table || (resample != 0) != (d_yuv_out != nullptr) || jp->quality < 1 || jp->quality > 100) {
+        err = "stub: JPEG launch without buffers or parameters";
+        return MVHP_FAILURE;
+    }
+    const size_t pb = mvhp_packed_frame_bytes(p), yb = mvhp_yuv_frame_bytes(p), gy = mvhp_geometry_yuv_bytes(g);
+    if (cap != (size_t)n * gy) { err = "stub: the blob is not n raw pictures long"; return MVHP_FAILURE; }
+    for (int i = 0; i < n; i++)
+        expand_compact((const uint8_t *)d_compact + (size_t)i * stride, (size_t)p->width_mbs * p->height_mbs, (uint8_t *)d_packed + (size_t)i * pb);
+    memset(d_yuv_coded, 0x11, (size_t)n * yb);
+    if (d_yuv_out) memset(d_yuv_out, 0x12, (size_t)n * gy);
+    size_t pos = 0;
+    for (int i = 0; i < n; i++) {
+        const uint64_t h = checksum((const uint8_t *)d_packed + (size_t)i * pb, pb);
+        const size_t len = stub_jpeg_length(h, gy);
+        mvhp_jpeg_entry_t e{pos, 0, MVHP_JPEG_TOO_BIG};
+        if (!stub_jpeg_too_big(h) && pos + len <= cap) {
+            memset(d_blob + pos, 0x3c, len);
+            memcpy(d_blob + pos, &h, sizeof(h));
+            d_blob[pos + len - 1] = kLastJpeg;
+            e.length = (uint32_t)len;
+            e.status = MVHP_JPEG_OK;
+            pos = (pos + len + 15) & ~(size_t)15;
+        }
+        d_table[i] = e;
+    }
+    std::this_thread::sleep_for(std::chrono::microseconds(200));
+    if (ms) *ms = 0.2f;
+    if (layout) *layout = MVHP_LAYOUT_ROWS;
+    if (waves) *waves = 8;
+    return MVHP_SUCCESS;
+}
+
 const mvengine::DeviceApi g_stub = {stub_device_count, stub_host_alloc, stub_host_free, stub_ctx_create, stub_ctx_destroy,
                                     stub_dev_alloc, stub_dev_free, stub_dev_free_bytes, stub_copy_n, stub_copy_n, stub_recon,
                                     nullptr, nullptr,   // (no placed arena on the stub device)
-                                    stub_recon_geometry};
+                                    stub_recon_geometry, stub_recon_jpeg};
 
 uint64_t picture_checksum(const mvhp_stream &s, int idr)
 {
@@ -209,6 +253,43 @@ struct CheckG {
             memcpy(&got, rgb + 8, 8);
             if (got != h || rgb[0] != 0xa5 || rgb[gr - 1] != (coded ? 0xa5 : kLastRgb)) c.bad++;
         } else if (rgb) c.bad++;
+        c.ok++;
+        return 1;
+    }
+};
+
+// sink of the JPEG mode: no planes, the stub's file of the right picture in `rgb`, its length in g->reserved[0]; the failures
+// are the geometries that cannot be formed and the pictures the stub reports too big
+struct CheckJ {
+    const mvhp_stream *s = nullptr;
+    mvhp_output_request_t req{};
+    int calls = 0, ok = 0, failed = 0, too_big = 0, bad = 0, next_seq = 0;
+    uint64_t bytes = 0;   // what the downloader had to move: 16 per picture in a batch + the files
+    std::vector<int> order;
+    static int sink(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *, const mvhp_output_geometry_t *g,
+                    const uint8_t *yuv, const uint8_t *rgb)
+    {
+        CheckJ &c = *static_cast<CheckJ *>(user);
+        c.calls++;
+        if (seq != c.next_seq || idr != c.order[(size_t)seq] || !g || yuv) c.bad++;
+        c.next_seq = seq + 1;
+        mvhp_output_geometry_t want;
+        const bool formed = mvhp_output_geometry(c.s, idr, &c.req, &want) == MVHP_SUCCESS;
+        const uint64_t h = picture_checksum(*c.s, idr);
+        if (formed) c.bytes += sizeof(mvhp_jpeg_entry_t);
+        if (rc != MVHP_SUCCESS) {
+            c.failed++;
+            if (formed) c.too_big++;
+            if (!err || !*err || rgb || (formed && !stub_jpeg_too_big(h))) c.bad++;
+            return 0;
+        }
+        const size_t len = formed ? stub_jpeg_length(h, mvhp_geometry_yuv_bytes(&want)) : 0;
+        want.reserved[0] = (uint32_t)len;
+        if (!formed || !rgb || stub_jpeg_too_big(h) || memcmp(&want, g, sizeof(want)) != 0) { c.bad++; return 0; }
+        uint64_t got = 0;
+        memcpy(&got, rgb, 8);
+        if (got != h || rgb[8] != 0x3c || rgb[len - 1] != kLastJpeg) c.bad++;
+        c.bytes += len;
         c.ok++;
         return 1;
     }
@@ -718,6 +799,60 @@ int main(int argc, char **argv)
             rmdir(dir);
         }
         printf("GEOMETRY MODE DONE\n");
+        if (argc > 5 && !strcmp(argv[5], "jpeg")) {   // ---- JPEG mode: MVHP_OUT_JPEG against the stub's JPEG operation ----
+            auto run_jpeg = [&](const char *name, mvhp_engine_opts_t o, const mvhp_stream &st, const std::vector<int> &order, int wanted,
+                                const mvhp_output_request_t &req, CheckJ &c, mvhp_decode_stats_t &stats) {
+                mvhp_engine_t *e = nullptr;
+                if (mvhp_engine_create(&o, &e) != MVHP_SUCCESS) { failures++; return MVHP_FAILURE; }
+                c.s = &st; c.req = req; c.order = order;
+                const int rc = mvhp_engine_decode_ex(e, &st, order.data(), (int)order.size(), wanted, MVHP_OUT_JPEG, &req, CheckJ::sink, &c, &stats);
+                mvhp_engine_destroy(e);
+                printf("%-28s rc=%d issued=%u ok=%u failed=%u (too big %d) batches=%u geometry=%u requeued=%u d2h=%llu\n", name, rc,
+                       stats.pictures_issued, stats.pictures_ok, stats.pictures_failed, c.too_big, stats.batches, stats.geometry_launches,
+                       stats.batches_requeued, (unsigned long long)stats.d2h_bytes);
+                return rc;
+            };
+            std::vector<int> order;
+            for (int k = 0; k < 3 * n3; k++) order.push_back(k % n3);
+            int unformed = 0, big = 0;
+            for (int idr : order) {
+                mvhp_output_geometry_t g;
+                if (mvhp_output_geometry(&s3, idr, &box, &g) != MVHP_SUCCESS) unformed++;
+                else if (stub_jpeg_too_big(picture_checksum(s3, idr))) big++;
+            }
+            for (int contexts = 1; contexts <= 3; contexts++)
+                for (mvhp_output_request_t req : {mvhp_output_request_t{0, 0, 0, 0}, crop, box}) {
+                    req.reserved = MVHP_JPEG_REQUEST(contexts == 2 ? 0 : 90, contexts == 3 ? 2 : 0);
+                    mvhp_engine_opts_t o = base; o.contexts = contexts; o.chunk_pictures = 2; o.batch_pictures = contexts == 1 ? 64 : 3;
+                    o.fail_context = contexts == 3 ? 0 : -1;   // three contexts: the first batch of context 0 fails and is re-queued
+                    CheckJ c; mvhp_decode_stats_t st;
+                    const int before = g_jpeg_calls, recon_before = g_recon_calls + g_geometry_calls;
+                    EXPECT(run_jpeg(req.flags & MVHP_OUTPUT_BOX ? "jpeg box" : req.flags ? "jpeg crop" : "jpeg coded size", o, s3, order,
+                                    (int)order.size(), req, c, st) == MVHP_SUCCESS);
+                    EXPECT(c.bad == 0 && c.calls == (int)order.size() && c.ok + c.failed == c.calls && c.ok == (int)st.pictures_ok);
+                    if (req.flags & MVHP_OUTPUT_BOX) EXPECT(c.failed == unformed + big && c.too_big == big);
+                    if (!req.flags) EXPECT(st.geometry_launches == 0);
+                    EXPECT(st.d2h_bytes == c.bytes && (int)st.batches == g_jpeg_calls - before);
+                    EXPECT(g_recon_calls + g_geometry_calls == recon_before);   // every launch of a JPEG call is the JPEG operation
+                    EXPECT((int)st.batches_requeued == (contexts == 3 ? 1 : 0));
+                }
+            EXPECT(big >= 1 && unformed >= 1);
+            {   // `wanted` caps the call: failed pictures (too big) do not count towards it
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 4;
+                CheckJ c; mvhp_decode_stats_t st;
+                EXPECT(run_jpeg("jpeg wanted = 5", o, s3, order, 5, box, c, st) == MVHP_SUCCESS);
+                EXPECT(c.bad == 0 && c.ok == 5 && st.pictures_ok == 5);
+            }
+            {   // the plain sink cannot take a file's length: refused
+                mvhp_engine_opts_t o = base; o.contexts = 1;
+                mvhp_engine_t *e = nullptr;
+                EXPECT(mvhp_engine_create(&o, &e) == MVHP_SUCCESS);
+                Check c; mvhp_decode_stats_t st;
+                EXPECT(mvhp_engine_decode(e, &s3, o3.data(), n3, n3, MVHP_OUT_JPEG, Check::sink, &c, &st) == MVHP_FAILURE);
+                mvhp_engine_destroy(e);
+            }
+            printf("JPEG MODE DONE\n");
+        }
     }
     EXPECT(g_live_ctx == 0 && g_dev_allocs == 0);
     printf(failures ? "HARNESS FAILED (%d)\n" : "HARNESS OK\n", failures);

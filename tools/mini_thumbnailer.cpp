@@ -61,12 +61,13 @@ int main(int argc, char *argv[])
             else fprintf(stderr, "-e : No valid extraction mode specified\n");
         } else if (!strcmp(argv[i], "-c")) setenv("MINIVIDEO_CROP", "1", 1);
         else if (!strcmp(argv[i], "-s") && has) setenv("MINIVIDEO_THUMBNAIL", argv[++i], 1);   // (the library checks the value)
+        else if (!strcmp(argv[i], "-j")) setenv("MINIVIDEO_JPEG", "1", 1);   // -f jpg writes JPEG files (made on the GPU), not the PNG fallback
         else if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) help = true;
         else fprintf(stderr, "* Unknown argument '%s'\n", argv[i]);
     }
     if (!in || help) {
         printf("* Usage:\nmini_thumbnailer -i <filepath> [-o <directory>] [-f picture_format][-q picture_quality]"
-               "[-n picture_number] [-e extraction_mode] [-c] [-s <width>x<height>]\n");
+               "[-n picture_number] [-e extraction_mode] [-c] [-s <width>x<height>] [-j]\n");
         return EXIT_FAILURE;
     }
     mark("main, arguments read");
