@@ -27,6 +27,18 @@
  *     baseline JFIF files coded on the GPU from the 4:2:0 planes as export.c:341-430 does with libjpeg (2x2 / 1x1 / 1x1
  *     sampling, no colour conversion), at picture_quality (clamped to 1 ... 100; otherwise this argument is unused), of the
  *     coded size or of the size MINIVIDEO_CROP / MINIVIDEO_THUMBNAIL ask for.  The other formats are not affected;
+ *   - opt-in, outside the reference's behaviour and independent of the switches above: MINIVIDEO_SKIP_BLANK=1 replaces blank
+ *     pictures -- black lead-ins, fades, flat title cards -- by later ones.  Every decoded picture gets a score on the GPU,
+ *     the variance of its luma samples (of the SPS's cropped rectangle under MINIVIDEO_CROP / MINIVIDEO_THUMBNAIL, else of the
+ *     coded picture) in sixteenths, and is blank when the score is below 16 x MINIVIDEO_BLANK_VARIANCE (an integer 0 ...
+ *     16256, default 256).  First every picture is written as without the switch, under the same names.  Then, for each file
+ *     whose picture is blank, up to MINIVIDEO_BLANK_ALTERNATES (1 ... 16, default 4) of the IDR pictures between it and the
+ *     next selected picture (to the end of the stream behind the last one) are decoded in stream order, and the file is
+ *     written again with the first of them that is not blank or, if there is none, with the highest-scoring of them all, the
+ *     original included (the earliest on a tie).  A replacement is written to <name>.part and renamed over the file: if that
+ *     write fails, the file keeps the picture it had.  The number of files, their names, the return value and picture_number mean
+ *     what they mean without the switch, and the files do not depend on batch sizes, threads or devices.  A malformed value
+ *     of any of the three variables is not ignored: minivideo_decode() returns FAILURE with a message before any device work;
  *   - H.264 IDR pictures only, from Annex-B elementary streams (.264/.h264 or a
  *     file starting with an SPS start code) or from the first H.264 video track
  *     of an MP4/MOV file (demuxer/mp4/mp4.c:1950 mp4_fileParse -> sync samples).

@@ -262,6 +262,8 @@ typedef struct mvhp_output_geometry {
 
 #define MVHP_OUTPUT_CROP 1u   /* mvhp_output_request_t::flags: pictures are the SPS's cropped rectangle         */
 #define MVHP_OUTPUT_BOX  2u   /* ... fitted into box_w x box_h (implies MVHP_OUTPUT_CROP); box sides >= 2     */
+#define MVHP_OUTPUT_SCORE 4u  /* mvhp_engine_decode_ex: every picture's score in g->reserved[1] ("Picture scores" below); changes no
+                                 picture: a request with this flag alone still means pictures of the coded size */
 typedef struct mvhp_output_request {
     uint32_t flags;           /* MVHP_OUTPUT_*; 0 = the coded size (what the reference writes)                  */
     uint32_t box_w, box_h;
@@ -331,6 +333,33 @@ MVHP_EXPORT int    mvhp_jpeg_encode_dev(mvhp_ctx_t *ctx, const mvhp_output_geome
                                         const uint8_t *d_yuv, int n, uint8_t *d_blob, size_t cap_bytes,
                                         mvhp_jpeg_entry_t *d_table, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Picture scores (opt-in; DESIGN.md 3 "Picture scores"): how much a picture shows, measured on the device as the variance of
+ * its luma samples, so that a caller can pass over black lead-ins, fades and flat title cards (minivideo_decode does under
+ * MINIVIDEO_SKIP_BLANK=1, include/minivideo.h).  The device sums; the score is integer arithmetic on the host.
+ * ------------------------------------------------------------------------- */
+typedef struct mvhp_luma_stats {   /* 32 bytes, 8-byte aligned */
+    uint64_t sum;        /* of the luma samples of the rectangle   */
+    uint64_t sumsq;      /* of their squares                       */
+    uint32_t samples;    /* crop_w * crop_h (<= 2^28)              */
+    uint32_t reserved[3];/* 0                                      */
+} mvhp_luma_stats_t;
+/* floor(16 (N Q - S^2) / N^2) with N = samples, S = sum, Q = sumsq: the luma variance in sixteenths, 0 ... 260100 (half the
+ * samples 0, half 255).  128-bit integer arithmetic, no floating point; N = 0 gives 0.  This integer is the only form of the
+ * score: thresholds compare it, ties are decided on it.  A host function: needs no device. */
+MVHP_EXPORT uint32_t mvhp_luma_score(const mvhp_luma_stats_t *st);
+/* Over a slot's candidates in order (the primary first): the index of the first whose score is at least min_score; if there
+ * is none, of the largest score, the earliest on a tie.  n <= 0: -1.  A host function. */
+MVHP_EXPORT int      mvhp_blank_choose(const uint32_t *scores, int n, uint32_t min_score);
+/* n coded pictures (d_yuv_coded: mvhp_yuv_frame_bytes(p) apart, 16-byte aligned, luma pitch 16 W) -> n records in d_stats
+ * (8-byte aligned), each over the luma rectangle crop_x, crop_y, crop_w, crop_h of g (all even, inside the coded picture, at
+ * least 2 x 2; out_w / out_h are not read: the score is a property of the source picture, whatever size is delivered).  n = 0
+ * does nothing; n < 0, a rectangle outside the picture, odd or zero sizes are refused (MVHP_FAILURE) before anything is
+ * launched.  Asynchronous on `stream` (NULL = the context's own); the call zeroes the records on that stream itself.  Nothing
+ * survives a launch and no kernel waits: safe under stream capture, and two calls on two streams do not meet. */
+MVHP_EXPORT int      mvhp_luma_stats_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                                         const uint8_t *d_yuv_coded, int n, mvhp_luma_stats_t *d_stats, void *stream);
+
 /* Page-locked host memory for the host-buffer entry points (H2D / D2H at full PCIe rate). */
 MVHP_EXPORT void *mvhp_host_alloc(size_t bytes);
 MVHP_EXPORT void  mvhp_host_free(void *p);
@@ -373,6 +402,11 @@ MVHP_EXPORT int  mvhp_set_fused_color(mvhp_ctx_t *ctx, int on);
  * (global memory to global memory, no LDS row buffers: their width limit does not apply); 0: on the general resample kernel,
  * for which such a geometry is one tap of 2^14 per axis, i.e. the same bytes.  Speed only, never results. */
 MVHP_EXPORT int  mvhp_set_crop_copy(mvhp_ctx_t *ctx, int on);
+
+/* Test-only knob, like the tuning knobs below (speed only, never results; not meant for products): luma rows per workgroup of
+ * mvhp_luma_stats_dev, 1 ... 65536; 0 (default) = sixteen, fewer when the grid would leave compute units idle.  It exists so that
+ * a test can force band sizes and compare the records: the sums are integers, every value gives the same 32 bytes. */
+MVHP_EXPORT int  mvhp_set_stats_band(mvhp_ctx_t *ctx, int rows);
 
 /* Tuning knob (speed only, never results): waves per picture workgroup, or macroblock rows per band of the banded forms
  * (1, 2, 4, 6, 8, 12 or 16; a layout that is not built for the value takes the next smaller one it is built for, or its
@@ -494,6 +528,12 @@ MVHP_EXPORT void mvhp_engine_destroy(mvhp_engine_t *e);
  * entries (16 bytes per picture) and the files' bytes. */
 #define MVHP_OUT_JPEG     4
 #define MVHP_JPEG_REQUEST(quality, restart_mcus) (((uint32_t)(quality) & 0xffu) | (((uint32_t)(restart_mcus) & 0xffffu) << 8))
+/* MVHP_OUTPUT_SCORE in mvhp_output_request_t::flags (mvhp_engine_decode_ex only; composes with MVHP_OUTPUT_CROP / _BOX and every
+ * output kind above): behind whatever reconstructs the batch (and the deblocking filter, where the stream asks for it)
+ * mvhp_luma_stats_dev sums the coded planes over each picture's crop rectangle, the 32-byte records come back with the
+ * pictures, and the sink finds g->reserved[1] = mvhp_luma_score of the picture's record (g->reserved[0] stays the JPEG length).
+ * Without the flag g->reserved[1] is 0 and there is no extra launch, buffer or byte; with it d2h_bytes grows by exactly 32 per
+ * delivered picture.  The pictures themselves are the same bytes either way. */
 /* Decode the pictures order[0..n_order) of `s` (IDR indices) until `wanted` of them have been accepted by the sink
  * (the reference stops after picture_number IDRs, h264.c:173-179: no more pictures than needed are entropy-decoded).
  * sink may be NULL (every reconstructed picture counts as accepted).  Returns MVHP_SUCCESS when `wanted` pictures

@@ -12,6 +12,7 @@
 #include <string>
 
 #include "decode_engine.h"
+#include "blank_policy.h"
 #include "launch_plan.h"
 #include "minivideo_hotpath.h"
 #include "recon_kernels.h"
@@ -58,6 +59,7 @@ struct mvhp_ctx {
     int          layout;      // MVHP_LAYOUT_*
     int          fused_color; // 1 = RGB written by the reconstruction kernel's epilogue (default)
     int          crop_copy;   // 1 = crop-only geometries run the copy kernel (crop_copy.hip), 0 = the general resample kernel
+    int          stats_band;  // luma rows per workgroup of the picture-score kernel, 0 = choose (mvhp_set_stats_band)
     int          n_cus;
     size_t       max_lds;
     int          last_layout, last_waves;   // what the last reconstruction launch used
@@ -211,6 +213,13 @@ MVHP_EXPORT int mvhp_set_crop_copy(mvhp_ctx_t *c, int on)
 {
     if (!c) return MVHP_FAILURE;
     c->crop_copy = on ? 1 : 0;
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT int mvhp_set_stats_band(mvhp_ctx_t *c, int rows)
+{
+    if (!c || rows < 0 || rows > 65536) return MVHP_FAILURE;
+    c->stats_band = rows;
     return MVHP_SUCCESS;
 }
 
@@ -441,6 +450,49 @@ static int ensure(void **ptr, size_t *have, size_t need)
     *have = 0;
     HIP_TRY(hipMalloc(ptr, need));
     *have = need;
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT uint32_t mvhp_luma_score(const mvhp_luma_stats_t *st)
+{
+    return st ? mvblank::luma_score(st->sum, st->sumsq, st->samples) : 0;
+}
+
+MVHP_EXPORT int mvhp_blank_choose(const uint32_t *scores, int n, uint32_t min_score) { return mvblank::choose(scores, n, min_score); }
+
+MVHP_EXPORT int mvhp_luma_stats_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                                    const uint8_t *d_yuv_coded, int n, mvhp_luma_stats_t *d_stats, void *stream)
+{
+    if (!c || !params_ok(p) || !g || !d_yuv_coded || n < 0 || ((uintptr_t)d_yuv_coded & 15) || !d_stats || ((uintptr_t)d_stats & 7)) {
+        set_err("mvhp_luma_stats_dev: invalid argument");
+        return MVHP_FAILURE;
+    }
+    const uint32_t Wp = p->width_mbs * 16, Hp = p->height_mbs * 16;
+    if (((g->crop_x | g->crop_y | g->crop_w | g->crop_h) & 1u) || g->crop_w < 2 || g->crop_h < 2 || g->crop_x > Wp ||
+        g->crop_w > Wp - g->crop_x || g->crop_y > Hp || g->crop_h > Hp - g->crop_y) {
+        set_err("mvhp_luma_stats_dev: rectangle %u,%u %ux%u of a %ux%u picture (even offsets and sizes of at least 2, inside the picture)",
+                g->crop_x, g->crop_y, g->crop_w, g->crop_h, Wp, Hp);
+        return MVHP_FAILURE;
+    }
+    if ((uint64_t)g->crop_w * g->crop_h > ((uint64_t)1 << 28)) {   // `samples` and the score's arithmetic are sized for this
+        set_err("mvhp_luma_stats_dev: rectangles of %u x %u are too large (at most 2^28 samples)", g->crop_w, g->crop_h);
+        return MVHP_UNSUPPORTED;
+    }
+    if (n == 0) return MVHP_SUCCESS;
+    HIP_TRY(hipSetDevice(c->device));
+    mvhp::LumaStatsArgs a;
+    a.src = d_yuv_coded;
+    a.frame_bytes = mvhp_yuv_frame_bytes(p);
+    a.n = n;
+    a.pitch = (int)Wp;
+    a.cx = (int)g->crop_x; a.cy = (int)g->crop_y; a.cw = (int)g->crop_w; a.ch = (int)g->crop_h;
+    // luma rows per workgroup: sixteen (at 1080p 1920 blocks of 16 bytes, 7.5 per lane), fewer when the grid would leave CUs
+    // idle -- the rule of the crop copy above.  Speed only: the sums are integers, any band size gives the same record.
+    int band = c->stats_band > 0 ? c->stats_band : 16;
+    while (c->stats_band <= 0 && band > 1 && (double)n * ((a.ch + band - 1) / band) < 4.0 * c->n_cus) band /= 2;
+    a.band = band;
+    a.stats = d_stats;
+    HIP_TRY(mvhp::launch_luma_stats(a, stream_of(c, stream)));
     return MVHP_SUCCESS;
 }
 
@@ -791,6 +843,21 @@ int eng_recon_jpeg(DevCtx *d, const mvhp_stream_params_t *p, const mvhp_output_g
                           layout, waves, err, &j);
 }
 
+// the picture scores of a batch: mvhp_luma_stats_dev on the coded planes the reconstruction left in d_yuv_coded, on the context's
+// stream behind it; returns when the records are written
+int eng_luma_stats(DevCtx *d, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const uint8_t *d_yuv_coded, int n,
+                   mvhp_luma_stats_t *d_stats, float *ms, std::string &err)
+{
+    mvhp_ctx *c = d->c;
+    ENG_TRY(hipSetDevice(c->device));
+    ENG_TRY(hipEventRecord(d->ev[2], c->stream));
+    if (mvhp_luma_stats_dev(c, p, g, d_yuv_coded, n, d_stats, c->stream) != MVHP_SUCCESS) { err = mvhp_last_error(); return MVHP_FAILURE; }
+    ENG_TRY(hipEventRecord(d->ev[3], c->stream));
+    ENG_TRY(hipEventSynchronize(d->ev[3]));
+    if (ms) ENG_TRY(hipEventElapsedTime(ms, d->ev[2], d->ev[3]));
+    return MVHP_SUCCESS;
+}
+
 // the engine's batch buffers from one placed arena (MINIVIDEO_PLACED=1): records / planes / RGB of a batch in three groups of
 // the device's memory regions (placement.hip); the compact staging area goes wherever room is left
 void *eng_placed_alloc(DevCtx *d, int sets, const size_t bytes[4], void **ptrs)
@@ -828,7 +895,7 @@ void eng_placed_free(DevCtx *d, void *arena)
 const mvengine::DeviceApi g_hip_api = {
     mvhp_device_count, mvhp_host_alloc, mvhp_host_free, eng_ctx_create, eng_ctx_destroy, eng_dev_alloc, eng_dev_free,
     eng_dev_free_bytes, eng_h2d, eng_d2h, eng_recon, eng_placed_alloc, eng_placed_free, eng_recon_geometry,
-    eng_recon_jpeg,
+    eng_recon_jpeg, eng_luma_stats,
 };
 
 } // namespace

@@ -123,4 +123,16 @@ hipError_t launch_jpeg_encode(const JpegArgs &a, hipStream_t stream);
 void       jpeg_quant_tables(int quality, uint8_t out[128]);
 void       jpeg_header(int w, int h, int quality, int restart, uint8_t out[MVHP_JPEG_HEADER_BYTES]);
 
+// picture scores (luma_stats.hip): sum and sum of squares of the luma samples of one rectangle of every picture
+struct LumaStatsArgs {
+    const uint8_t     *src;          // n coded pictures, 16-byte aligned
+    size_t             frame_bytes;  // from one picture to the next (a multiple of 16)
+    int                n;
+    int                pitch;        // of the luma plane, a multiple of 16
+    int                cx, cy, cw, ch;   // the rectangle, inside the picture, cw and ch at least 1
+    int                band;         // luma rows per workgroup
+    mvhp_luma_stats_t *stats;        // n records, 8-byte aligned
+};
+hipError_t launch_luma_stats(const LumaStatsArgs &a, hipStream_t stream);
+
 } // namespace mvhp

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "decode_engine.h"
+#include "blank_policy.h"
 #include "export.h"
 #include "h264_frontend.h"
 #include "minivideo.h"
@@ -305,6 +306,9 @@ struct ExportSink {
     bool closing = false;
     std::atomic<int> written{0}, write_errors{0};
     bool stopped_by_write_error = false;
+    // MINIVIDEO_SKIP_BLANK=1: what each slot (the _k of the file name) holds after pass 1 -- its IDR, its score, its file
+    struct Slot { int idr; uint32_t score; std::string name; };
+    std::vector<Slot> *slots = nullptr;
 
     // file_bytes: PICTURE_JPG under MINIVIDEO_JPEG=1 only -- `rgb` then is the finished file (made on the device)
     int write_one(const std::string &name, int W, int H, const uint8_t *yuv, const uint8_t *rgb, size_t file_bytes) const
@@ -379,6 +383,7 @@ struct ExportSink {
         const int W = (int)g->out_w, H = (int)g->out_h;   // the coded size unless MINIVIDEO_CROP / MINIVIDEO_THUMBNAIL ask for less
         const size_t file_bytes = x.fmt == PICTURE_JPG ? g->reserved[0] : 0;   // (MVHP_OUT_JPEG: the length of the file in `rgb`)
         if (!x.pool.empty()) {
+            if (x.write_errors.load() == 0 && x.slots) x.slots->push_back(Slot{idr, g->reserved[1], name});
             // Writers run behind the pipeline, so a write that fails is only known later: no further picture is decoded in
             // its place (the synchronous path below does that).  Once one has failed -- a full disk does not get better --
             // decoding stops, and minivideo_decode answers FAILURE unless every wanted file was written (contract: minivideo.h).
@@ -398,8 +403,57 @@ struct ExportSink {
             x.errors++;
             return 0;
         }
+        if (x.slots) x.slots->push_back(Slot{idr, g->reserved[1], name});
         x.exported++;
         x.written++;
+        return 1;
+    }
+};
+
+// ---- MINIVIDEO_SKIP_BLANK=1, pass 2 (include/minivideo.h; DESIGN.md 3 "Picture scores"): the alternates of the blank slots, decoded
+// in one more engine call.  A slot's file is written again -- on the calling thread: two writes to one name must land in order --
+// whenever mvhp_blank_choose over the scores seen so far for the slot (the primary first) moves to the new candidate.
+struct AlternateSink {
+    ExportSink *x = nullptr;                        // the writer of pass 1 (format, counters)
+    std::vector<ExportSink::Slot> *slots = nullptr;
+    std::vector<int> slot_of;                       // per picture of pass 2's order: its slot
+    std::vector<std::vector<uint32_t>> scores;      // per slot: the primary's score, then its alternates' as they arrive
+    uint32_t min_score = 0;
+    int replaced = 0;
+
+    static int call(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *p,
+                    const mvhp_output_geometry_t *g, const uint8_t *yuv, const uint8_t *rgb)
+    {
+        (void)p;
+        AlternateSink &a = *static_cast<AlternateSink *>(user);
+        ExportSink &x = *a.x;
+        if (rc != MVHP_SUCCESS) {   // a failed alternate is skipped
+            log_err("IDR %d: %s", idr, err ? err : "failed");
+            if (++x.errors > 64) { x.aborted = true; return -1; }   // h264.c:181-187
+            return 0;
+        }
+        x.errors = 0;
+        const int k = a.slot_of[(size_t)seq];
+        std::vector<uint32_t> &sc = a.scores[(size_t)k];
+        if (sc[(size_t)mvblank::choose(sc.data(), (int)sc.size(), a.min_score)] >= a.min_score) return 1;   // the slot is settled
+        sc.push_back(g->reserved[1]);
+        if (mvblank::choose(sc.data(), (int)sc.size(), a.min_score) != (int)sc.size() - 1) return 1;
+        ExportSink::Slot &slot = (*a.slots)[(size_t)k];
+        const size_t file_bytes = x.fmt == PICTURE_JPG ? g->reserved[0] : 0;
+        // beside the slot's file first, then renamed over it: a write that fails leaves the file of the earlier candidate whole,
+        // which is what `written` counted.  The candidate is then taken out of the slot's scores again, so that a later
+        // alternate is weighed against what the file holds.
+        const std::string part = slot.name + ".part";
+        if (!x.write_one(part, (int)g->out_w, (int)g->out_h, yuv, rgb, file_bytes) || rename(part.c_str(), slot.name.c_str()) != 0) {
+            log_err("Unable to write '%s'", slot.name.c_str());
+            (void)unlink(part.c_str());
+            sc.pop_back();
+            x.errors++;
+            return 0;
+        }
+        slot.idr = idr;
+        slot.score = g->reserved[1];
+        a.replaced++;
         return 1;
     }
 };
@@ -526,6 +580,12 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
         std::string why;
         if (!output_request_from_env(req, why)) { log_err("%s", why.c_str()); return FAILURE; }
     }
+    mvblank::Settings blank;
+    {   // the same for the blank-picture switches
+        std::string why;
+        if (!mvblank::settings_from(getenv("MINIVIDEO_SKIP_BLANK"), getenv("MINIVIDEO_BLANK_VARIANCE"),
+                                    getenv("MINIVIDEO_BLANK_ALTERNATES"), blank, why)) { log_err("%s", why.c_str()); return FAILURE; }
+    }
 
     // The engine (HIP runtime, one context per device, its thread pools: 0.2-0.5 s in a fresh process) comes up on a thread
     // of its own while this one reads and indexes the file.
@@ -614,9 +674,40 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     // RGB formats are written from the RGB picture alone: the planes stay on the device
     // JPEG files come back finished: only their bytes are downloaded and written
     if (jpeg) req.reserved = MVHP_JPEG_REQUEST(std::min(100, std::max(1, picture_quality)), 0);
-    (void)mvhp_engine_decode_ex(eng, &s, order.data(), (int)order.size(), wanted, jpeg ? MVHP_OUT_JPEG : want_rgb ? MVHP_OUT_RGB_ONLY : 0,
+    // opt-in (MINIVIDEO_SKIP_BLANK=1, outside the parity contract): the same call with every picture's score, pass 1 of 2
+    std::vector<ExportSink::Slot> slots;
+    if (blank.on) { req.flags |= MVHP_OUTPUT_SCORE; sink.slots = &slots; }
+    const int out_kind = jpeg ? MVHP_OUT_JPEG : want_rgb ? MVHP_OUT_RGB_ONLY : 0;
+    (void)mvhp_engine_decode_ex(eng, &s, order.data(), (int)order.size(), wanted, out_kind,
                                 (req.flags || jpeg) ? &req : nullptr, ExportSink::call, &sink, &st);
     sink.finish();   // (every kept picture is back: mvhp_engine_decode waits for that)
+    if (blank.on && !sink.aborted && sink.write_errors.load() == 0) {
+        // pass 2: the alternates of every slot whose picture scores below the threshold -- the IDRs between it and the next
+        // slot's picture (select_idrs' size filter does not apply to them).  Slots, scores and alternates are functions of
+        // the stream and the switches alone, and the sink sees pictures in the order of the list: the files do not depend on
+        // batch sizes, threads or contexts.
+        AlternateSink alt;
+        alt.x = &sink;
+        alt.slots = &slots;
+        alt.min_score = blank.min_score;
+        std::vector<int> idrs, order2;
+        for (const ExportSink::Slot &sl : slots) { idrs.push_back(sl.idr); alt.scores.push_back({sl.score}); }
+        int n_blank = 0;
+        for (int k = 0; k < (int)slots.size(); k++) {
+            if (slots[(size_t)k].score >= blank.min_score) continue;
+            n_blank++;
+            for (int i : mvblank::alternates(idrs, (int)s.idrs.size(), blank.alternates, k)) { order2.push_back(i); alt.slot_of.push_back(k); }
+        }
+        mvhp_decode_stats_t st2;
+        memset(&st2, 0, sizeof(st2));
+        if (!order2.empty())
+            (void)mvhp_engine_decode_ex(eng, &s, order2.data(), (int)order2.size(), (int)order2.size(), out_kind, &req,
+                                        AlternateSink::call, &alt, &st2);
+        if (getenv("MINIVIDEO_STATS"))
+            fprintf(stderr, "[minivideo] blank pictures: %d of %d slots score below %u; second pass: %d alternates listed, %u "
+                            "entropy-decoded, %d files replaced, %.3f s\n", n_blank, (int)slots.size(), blank.min_score,
+                    (int)order2.size(), st2.pictures_issued, alt.replaced, st2.wall_s);
+    }
     if (getenv("MINIVIDEO_STATS")) {
         fprintf(stderr, "[minivideo] decode call: reading the file %.3f s, indexing %.3f s, engine up after %.3f s (its thread took "
                         "%.3f s), decode %.3f s, %d file writers\n", t_read - t_call, t_indexed - t_read, t_engine - t_call, es.seconds,

@@ -29,6 +29,7 @@
 #include <thread>
 #include <vector>
 
+#include "blank_policy.h"
 #include "h264_frontend.h"
 #include "stream_internal.h"
 
@@ -114,6 +115,7 @@ struct InChunk {
 struct OutChunk {
     Pinned yuv, rgb;         // (MVHP_OUT_JPEG: rgb holds the files of the chunk's pictures, tab their table entries)
     Pinned tab;
+    Pinned stats;            // (MVHP_OUTPUT_SCORE: the records of the chunk's pictures)
     int refs = 0;            // pictures handed to the sink queue and not yet consumed
 };
 
@@ -144,6 +146,9 @@ struct DevBuf {
     // MVHP_OUT_JPEG: the encoder's blob (n x the raw picture) and table of a batch
     uint8_t *jpeg_blob = nullptr, *jpeg_tab = nullptr;
     size_t jpeg_blob_cap = 0, jpeg_tab_cap = 0;
+    // MVHP_OUTPUT_SCORE: the records of a batch (n x 32 bytes)
+    uint8_t *stats = nullptr;
+    size_t stats_cap = 0;
     void leave_arena()          // the four arena pieces are forgotten (they go with the arena); the output buffers stay
     {
         compact = packed = nullptr;
@@ -272,6 +277,7 @@ private:
     bool want_rgb_ = false, want_yuv_ = true;   // which outputs are downloaded (the planes are always reconstructed)
     bool want_jpeg_ = false;                    // MVHP_OUT_JPEG: neither of them; JPEG files made on the device are
     mvhp_jpeg_params_t jpeg_{};
+    bool score_ = false;                        // MVHP_OUTPUT_SCORE (taken out of req_.flags: it changes no picture and no path)
     mvhp_output_request_t req_{};               // flags 0: pictures of the coded size
     bool stop_ = false;
     bool sink_waiting_ = false;
@@ -303,7 +309,7 @@ private:
 Engine::~Engine()
 {
     for (auto &c : all_in_) api_.host_free(c->buf.p);
-    for (auto &c : all_out_) { api_.host_free(c->yuv.p); api_.host_free(c->rgb.p); api_.host_free(c->tab.p); }
+    for (auto &c : all_out_) { api_.host_free(c->yuv.p); api_.host_free(c->rgb.p); api_.host_free(c->tab.p); api_.host_free(c->stats.p); }
     for (Ctx &c : ctx_) {
         if (c.arena) {   // pieces of the arena go with it; a buffer that left the arena is freed below like any other
             for (DevBuf &b : c.bufs) if (b.arena_piece) b.leave_arena();
@@ -318,6 +324,7 @@ Engine::~Engine()
             if (b.out_rgb) api_.dev_free(c.dev, b.out_rgb);
             if (b.jpeg_blob) api_.dev_free(c.dev, b.jpeg_blob);
             if (b.jpeg_tab) api_.dev_free(c.dev, b.jpeg_tab);
+            if (b.stats) api_.dev_free(c.dev, b.stats);
         }
         if (c.dev) api_.ctx_destroy(c.dev);
     }
@@ -424,7 +431,8 @@ int Engine::batch_capacity(const mvhp_stream_params_t &p, const mvhp_output_geom
                               : (want_rgb_ ? mvhp_rgb_frame_bytes(&p) : 0)) +
                            // (the blob, 1 x the planes, and the encoder's scratch in the context, 136 bytes per 8x8 block = 2.125 x the planes
                            //  padded to whole MCUs: 3.125 x, budgeted as 4.25 x for that padding on small pictures)
-                           (want_jpeg_ ? (g ? mvhp_geometry_yuv_bytes(g) : mvhp_yuv_frame_bytes(&p)) * 17 / 4 : 0);
+                           (want_jpeg_ ? (g ? mvhp_geometry_yuv_bytes(g) : mvhp_yuv_frame_bytes(&p)) * 17 / 4 : 0) +
+                           (score_ ? sizeof(mvhp_luma_stats_t) : 0);
     size_t budget = ctx_[0].mem_budget;
     for (const Ctx &c : ctx_) budget = std::min(budget, c.mem_budget);
     const int mem_cap = (int)std::min<size_t>(1 << 20, std::max<size_t>(1, budget / std::max<size_t>(1, per_pic)));
@@ -542,7 +550,7 @@ bool Engine::ensure_devbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
 // change inside a job; these buffers are the small side of a batch)
 bool Engine::ensure_outbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
 {
-    if (!bt.use_geom && !want_jpeg_) return true;
+    if (!bt.use_geom && !want_jpeg_ && !score_) return true;
     const size_t n = (size_t)bt.capacity;
     auto need = [&](uint8_t **ptr, size_t *cap, size_t bytes) {
         if (*cap >= bytes) return true;
@@ -557,6 +565,10 @@ bool Engine::ensure_outbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
         }
         return *ptr != nullptr;
     };
+    if (score_ && !need(&b.stats, &b.stats_cap, n * sizeof(mvhp_luma_stats_t))) {
+        err = "out of device memory for the picture scores of a batch of " + std::to_string(bt.capacity);
+        return false;
+    }
     if (want_jpeg_ && (!need(&b.jpeg_blob, &b.jpeg_blob_cap, n * mvhp_geometry_yuv_bytes(&bt.geom)) ||
                        !need(&b.jpeg_tab, &b.jpeg_tab_cap, n * sizeof(mvhp_jpeg_entry_t)))) {
         err = "out of device memory for the JPEG files of a batch of " + std::to_string(bt.capacity);
@@ -934,6 +946,7 @@ void Engine::launcher(int k)
         int rc = MVHP_SUCCESS;
         const double t_call = now_s();
         if (inject) { rc = MVHP_FAILURE; err = "injected failure (test hook)"; }
+        else if (score_ && !api_.luma_stats) { rc = MVHP_FAILURE; err = "this device table has no picture-score operation"; }
         else if (want_jpeg_ && !api_.recon_jpeg) { rc = MVHP_FAILURE; err = "this device table has no JPEG operation"; }
         else if (want_jpeg_)
             rc = api_.recon_jpeg(cx.dev, &b->params, &b->geom, b->use_geom ? 1 : 0, &jpeg_, b->buf->compact,
@@ -949,6 +962,11 @@ void Engine::launcher(int k)
             rc = api_.recon_geometry(cx.dev, &b->params, &b->geom, b->buf->compact, compact_slot_bytes(b->params), b->buf->packed,
                                      b->total, b->buf->yuv, want_yuv_ ? b->buf->out_yuv : nullptr,
                                      want_rgb_ ? b->buf->out_rgb : nullptr, &ms, &layout, &waves, err);
+        if (rc == MVHP_SUCCESS && score_ && !inject) {   // the scores, from the coded planes the operation above left in the batch buffer
+            float ms_s = 0.f;
+            rc = api_.luma_stats(cx.dev, &b->params, &b->geom, b->buf->yuv, b->total, (mvhp_luma_stats_t *)b->buf->stats, &ms_s, err);
+            ms += ms_s;
+        }
         if (!cx.launched_once) {   // host time of the first call beyond the device time: code-object load, first-launch setup
             cx.launched_once = true;
             std::lock_guard<std::mutex> la(alloc_mu_);
@@ -1031,15 +1049,27 @@ void Engine::downloader(int k)
             }
             std::string err;
             float ms = 0.f, ms2 = 0.f;
+            // MVHP_OUTPUT_SCORE: the chunk's records travel with it, one more piece of the chunk's own download call
+            const mvhp_luma_stats_t *recs = nullptr;
+            const size_t score_bytes = score_ ? (size_t)n * sizeof(mvhp_luma_stats_t) : 0;
+            if (score_ && !grow(oc->stats, (size_t)C * sizeof(mvhp_luma_stats_t))) {
+                std::lock_guard<std::mutex> l(mu_);
+                put_out(oc);
+                fail = "out of page-locked host memory";
+                continue;
+            }
+            if (score_) recs = (const mvhp_luma_stats_t *)oc->stats.p;
             if (want_jpeg_) {   // the table rows of the chunk's pictures, then exactly the bytes they name, one piece per file
                 const mvhp_jpeg_entry_t *tab = nullptr;
                 size_t base = 0, span = 0, moved = (size_t)n * sizeof(mvhp_jpeg_entry_t);
                 bool ok = grow(oc->tab, (size_t)C * sizeof(mvhp_jpeg_entry_t));
                 if (!ok) err = "out of page-locked host memory";
                 if (ok) {
-                    void *dst = oc->tab.p;
-                    const void *src = b->buf->jpeg_tab + (size_t)g * sizeof(mvhp_jpeg_entry_t);
-                    ok = api_.d2h(cx.dev, 1, &dst, &src, &moved, &ms, err) == MVHP_SUCCESS;
+                    void *dst[2] = {oc->tab.p, oc->stats.p};
+                    const void *src[2] = {b->buf->jpeg_tab + (size_t)g * sizeof(mvhp_jpeg_entry_t),
+                                          score_ ? b->buf->stats + (size_t)g * sizeof(mvhp_luma_stats_t) : nullptr};
+                    size_t nb[2] = {moved, score_bytes};
+                    ok = api_.d2h(cx.dev, score_ ? 2 : 1, dst, src, nb, &ms, err) == MVHP_SUCCESS;
                     tab = (const mvhp_jpeg_entry_t *)oc->tab.p;
                 }
                 const size_t blob_cap = (size_t)b->total * mvhp_geometry_yuv_bytes(&b->geom);
@@ -1072,7 +1102,7 @@ void Engine::downloader(int k)
                     std::lock_guard<std::mutex> l(mu_);
                     if (ok) {
                         st_.d2h_s += (ms + ms2) * 1e-3;
-                        st_.d2h_bytes += moved;
+                        st_.d2h_bytes += moved + score_bytes;
                         oc->refs = 0;
                         for (int i = 0; i < n; i++) {
                             PicResult &r = results_[(size_t)b->seqs[(size_t)(g + i)]];
@@ -1087,6 +1117,7 @@ void Engine::downloader(int k)
                                 r.rc = MVHP_FAILURE;
                                 r.err = "the JPEG file does not fit into the room of the raw picture";
                             }
+                            if (recs) r.geom.reserved[1] = mvblank::luma_score(recs[i].sum, recs[i].sumsq, recs[i].samples);
                             r.yuv = nullptr;
                             r.ready = true;
                         }
@@ -1102,19 +1133,20 @@ void Engine::downloader(int k)
             bool ok = (!want_yuv_ || grow(oc->yuv, (size_t)C * yb)) && (!want_rgb_ || grow(oc->rgb, (size_t)C * rb));
             if (!ok) err = "out of page-locked host memory";
             if (ok) {
-                void *dst[2];
-                const void *src[2];
-                size_t nb[2];
+                void *dst[3];
+                const void *src[3];
+                size_t nb[3];
                 int np = 0;
                 if (want_yuv_) { dst[np] = oc->yuv.p; src[np] = d_y + (size_t)g * yb; nb[np++] = (size_t)n * yb; }
                 if (want_rgb_) { dst[np] = oc->rgb.p; src[np] = d_r + (size_t)g * rb; nb[np++] = (size_t)n * rb; }
+                if (score_) { dst[np] = oc->stats.p; src[np] = b->buf->stats + (size_t)g * sizeof(mvhp_luma_stats_t); nb[np++] = score_bytes; }
                 ok = api_.d2h(cx.dev, np, dst, src, nb, &ms, err) == MVHP_SUCCESS;
             }
             {
                 std::lock_guard<std::mutex> l(mu_);
                 if (ok) {
                     st_.d2h_s += (ms + ms2) * 1e-3;
-                    st_.d2h_bytes += (uint64_t)n * ((want_yuv_ ? yb : 0) + rb);
+                    st_.d2h_bytes += (uint64_t)n * ((want_yuv_ ? yb : 0) + rb) + score_bytes;
                     oc->refs = 0;
                     for (int i = 0; i < n; i++) {
                         PicResult &r = results_[(size_t)b->seqs[(size_t)(g + i)]];
@@ -1123,6 +1155,7 @@ void Engine::downloader(int k)
                         r.oc = oc;
                         r.yuv = want_yuv_ ? oc->yuv.p + (size_t)i * yb : nullptr;
                         r.rgb = want_rgb_ ? oc->rgb.p + (size_t)i * rb : nullptr;
+                        if (recs) r.geom.reserved[1] = mvblank::luma_score(recs[i].sum, recs[i].sumsq, recs[i].samples);
                         r.ready = true;
                         oc->refs++;
                     }
@@ -1154,7 +1187,7 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
                    mvhp_picture_sink_t sink, mvhp_picture_sink_ex_t sink_ex, void *user, mvhp_decode_stats_t *stats,
                    std::string &err)
 {
-    if (req && ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX)) || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2)))) {
+    if (req && ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_SCORE)) || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2)))) {
         err = "malformed output request (box sides must be at least 2)";
         return MVHP_FAILURE;
     }
@@ -1180,6 +1213,8 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
             jpeg_.restart_mcus = (rsv >> 8) & 0xffffu;
         }
         req_ = req ? *req : mvhp_output_request_t{};
+        score_ = (req_.flags & MVHP_OUTPUT_SCORE) != 0;
+        req_.flags &= ~MVHP_OUTPUT_SCORE;   // (what is left decides the geometry: none = the path of a call without a request)
         stop_ = false; sink_waiting_ = false;
         pos_ = issued_ = consumed_ = ok_ = failed_ = 0;
         next_batch_id_ = 0;

@@ -58,6 +58,11 @@ struct DeviceApi {
                          const mvhp_jpeg_params_t *jp, const void *d_compact, size_t stride, void *d_packed, int n_pictures,
                          uint8_t *d_yuv_coded, uint8_t *d_yuv_out, uint8_t *d_blob, size_t cap_bytes, mvhp_jpeg_entry_t *d_table,
                          float *ms, int *layout, int *waves, std::string &err);
+    // optional (may be NULL: a call with MVHP_OUTPUT_SCORE then fails), last for the same reason: mvhp_luma_stats_dev over the crop
+    // rectangle of g on the n coded planes that recon / recon_geometry / recon_jpeg left in d_yuv_coded (after the deblocking
+    // filter, where p asks for it) -> n records in d_stats; *ms = its device-side duration
+    int    (*luma_stats)(DevCtx *c, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const uint8_t *d_yuv_coded,
+                         int n_pictures, mvhp_luma_stats_t *d_stats, float *ms, std::string &err);
 };
 
 class Engine;

@@ -52,7 +52,7 @@ class StreamParams(C.Structure):
 
 
 OUT_JPEG = 4                                                            # mvhp_engine_decode_ex output kind (MVHP_OUT_JPEG)
-OUTPUT_CROP, OUTPUT_BOX = 1, 2                                          # mvhp_output_request_t flags (MVHP_OUTPUT_*)
+OUTPUT_CROP, OUTPUT_BOX, OUTPUT_SCORE = 1, 2, 4                          # mvhp_output_request_t flags (MVHP_OUTPUT_*)
 
 
 class OutputGeometry(C.Structure):
@@ -67,6 +67,11 @@ class OutputGeometry(C.Structure):
     @property
     def rgb_bytes(self):
         return int(self.out_w) * int(self.out_h) * 3
+
+    @property
+    def score(self):
+        """the picture's score (Engine.decode(score=True): MVHP_OUTPUT_SCORE), else 0"""
+        return int(self.reserved[1])
 
 
 class OutputRequest(C.Structure):
@@ -109,6 +114,29 @@ def jpeg_quant_tables(quality):
     if lib().mvhp_jpeg_quant_tables(int(quality), out.ctypes.data) != SUCCESS:
         raise MiniVideoError("mvhp_jpeg_quant_tables failed")
     return out.reshape(2, 64)
+
+
+class LumaStats(C.Structure):
+    """mvhp_luma_stats_t: sums over the luma samples of a picture's rectangle"""
+    _fields_ = [("sum", C.c_uint64), ("sumsq", C.c_uint64), ("samples", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+LUMA_STATS_DTYPE = np.dtype([("sum", "<u8"), ("sumsq", "<u8"), ("samples", "<u4"), ("reserved", "<u4", (3,))])
+
+
+def luma_score(stats):
+    """mvhp_luma_score: the luma variance of a LumaStats record (or a (sum, sumsq, samples) triple) in sixteenths, an integer
+    (no device needed)"""
+    if not isinstance(stats, LumaStats):
+        s, q, n = stats
+        stats = LumaStats(int(s), int(q), int(n))
+    return int(lib().mvhp_luma_score(C.byref(stats)))
+
+
+def blank_choose(scores, min_score):
+    """mvhp_blank_choose: index of the first score >= min_score, else of the largest (the earliest on a tie); -1 for none"""
+    arr = (C.c_uint32 * max(len(scores), 1))(*[int(x) for x in scores])
+    return int(lib().mvhp_blank_choose(arr, len(scores), int(min_score)))
 
 
 def geometry(crop_x, crop_y, crop_w, crop_h, out_w=None, out_h=None):
@@ -220,6 +248,14 @@ def lib():
         getattr(L, f).argtypes = [pg]
     L.mvhp_resample_dev.restype = i32
     L.mvhp_resample_dev.argtypes = [vp, pp, pg, vp, i32, vp, vp, vp]
+    L.mvhp_luma_score.restype = C.c_uint32
+    L.mvhp_luma_score.argtypes = [C.POINTER(LumaStats)]
+    L.mvhp_blank_choose.restype = i32
+    L.mvhp_blank_choose.argtypes = [C.POINTER(C.c_uint32), i32, C.c_uint32]
+    L.mvhp_luma_stats_dev.restype = i32
+    L.mvhp_luma_stats_dev.argtypes = [vp, pp, pg, vp, i32, vp, vp]
+    L.mvhp_set_stats_band.restype = i32
+    L.mvhp_set_stats_band.argtypes = [vp, i32]
     L.mvhp_jpeg_header_bytes.restype = sz
     L.mvhp_jpeg_header_bytes.argtypes = []
     L.mvhp_jpeg_quant_tables.restype = i32
@@ -328,6 +364,17 @@ class HotPath:
         rc = self._L.mvhp_resample_dev(self._h, C.byref(params), C.byref(geom), d_yuv_coded, int(n), d_yuv_out, d_rgb_out, stream)
         if rc != SUCCESS:
             raise _err(self._L, "mvhp_resample_dev")
+
+    def luma_stats_dev(self, params, geom, d_yuv_coded, n, d_stats, stream=None):
+        """n coded pictures (device) -> n LumaStats records (LUMA_STATS_DTYPE, device) over geom's crop rectangle.  Asynchronous."""
+        rc = self._L.mvhp_luma_stats_dev(self._h, C.byref(params), C.byref(geom), d_yuv_coded, int(n), d_stats, stream)
+        if rc != SUCCESS:
+            raise _err(self._L, "mvhp_luma_stats_dev")
+
+    def set_stats_band(self, rows):
+        """test-only: luma rows per workgroup of luma_stats_dev, 0 = choose (speed only: the records do not depend on it)"""
+        if self._L.mvhp_set_stats_band(self._h, int(rows)) != SUCCESS:
+            raise MiniVideoError("mvhp_set_stats_band(%d) failed" % rows)
 
     def jpeg_encode_dev(self, geom, d_yuv, n, d_blob, cap_bytes, d_table, quality=75, restart_mcus=0, stream=None, stages=0):
         """n pictures of OutputGeometry `geom` (planar, device) -> JPEG files in d_blob (16-byte aligned, cap_bytes) and n
@@ -487,7 +534,8 @@ class Engine:
         """gives back a picture whose sink call answered 2 (any thread; the decode call returns when the last one is back)"""
         self._L.mvhp_engine_release_picture(self._h, int(seq))
 
-    def decode(self, stream_handle, order, wanted=None, want_rgb=False, sink=None, output=None, jpeg=None, restart_mcus=0):
+    def decode(self, stream_handle, order, wanted=None, want_rgb=False, sink=None, output=None, jpeg=None, restart_mcus=0,
+               score=False):
         """sink(seq, idr, rc, err, params, yuv ndarray | None, rgb ndarray | None) -> 1 accept / 0 reject / -1 stop /
         2 accept and keep until release_picture(seq); the arrays are views of page-locked memory valid only during the call
         (or until the release).  Returns (rc, stats dict).
@@ -496,12 +544,16 @@ class Engine:
         copy): sink(seq, idr, rc, err, params, geometry, yuv, rgb), the arrays sized by it.
         jpeg = a quality (1 .. 100): MVHP_OUT_JPEG -- the pictures (of the coded size, or of `output`) are coded as JPEG on the
         device and only the files come back: sink(seq, idr, rc, err, params, geometry, None, file bytes as a uint8 array);
-        want_rgb is ignored; restart_mcus 0 = one MCU row."""
+        want_rgb is ignored; restart_mcus 0 = one MCU row.
+        score=True: MVHP_OUTPUT_SCORE -- the sink is called as for `output` (with the geometry, also for pictures of the coded
+        size) and finds each picture's score in geometry.score; the pictures are the same bytes."""
         order = (C.c_int * len(order))(*order)
         st = DecodeStats()
         n_wanted = len(order) if wanted is None else wanted
-        if output is not None or jpeg is not None:
+        if output is not None or jpeg is not None or score:
             req = output_request(output) or OutputRequest(0, 0, 0, 0)
+            if score:
+                req.flags |= OUTPUT_SCORE
             if jpeg is not None:
                 req.reserved = (min(max(int(jpeg), 1), 100) & 0xff) | ((int(restart_mcus) & 0xffff) << 8)
 

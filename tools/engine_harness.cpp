@@ -4,14 +4,16 @@
 // lets the sink check that the right picture arrives in the right place, in order, through chunks, batches, several
 // contexts and a re-queue.  Nothing here is part of libminivideo.so.
 //
-// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes>]]
+// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes> [jpeg | score]]]
 // The fourth argument adds the geometry mode: mvhp_engine_decode_ex and minivideo_decode under MINIVIDEO_CROP /
-// MINIVIDEO_THUMBNAIL against the stub's output-geometry operation.
+// MINIVIDEO_THUMBNAIL against the stub's output-geometry operation.  A fifth argument adds the JPEG mode (MVHP_OUT_JPEG) or the
+// score mode (MVHP_OUTPUT_SCORE against the stub's picture-score operation, which sums the stub's coded planes on the CPU).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -21,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "blank_policy.h"
 #include "decode_engine.h"
 #include "minivideo.h"
 #include "stream_internal.h"
@@ -120,6 +123,54 @@ int stub_recon(DevCtx *, const mvhp_stream_params_t *p, const void *d_compact, s
     return MVHP_SUCCESS;
 }
 
+// The coded planes the geometry and JPEG operations leave behind: 0x11, the luma plane filled with the eight bytes of the records'
+// checksum over and over, so that every rectangle of it sums to something that depends on the picture (score mode).  The plain
+// operation's planes are its output: 0x5a with the checksum in bytes 0-7.
+uint8_t coded_luma(uint64_t h, bool pattern, size_t j) { return pattern ? (uint8_t)(h >> (8 * (j & 7))) : j < 8 ? (uint8_t)(h >> (8 * j)) : 0x5a; }
+void fill_coded(uint8_t *pic, size_t yb, uint64_t h)
+{
+    memset(pic, 0x11, yb);
+    for (size_t j = 0; j < yb / 3 * 2; j++) pic[j] = coded_luma(h, true, j);
+}
+mvhp_luma_stats_t expected_stats(uint64_t h, bool pattern, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g)
+{
+    mvhp_luma_stats_t st{};
+    const size_t Wp = (size_t)p->width_mbs * 16;
+    for (uint32_t y = g->crop_y; y < g->crop_y + g->crop_h; y++)
+        for (uint32_t x = g->crop_x; x < g->crop_x + g->crop_w; x++) {
+            const uint64_t v = coded_luma(h, pattern, (size_t)y * Wp + x);
+            st.sum += v;
+            st.sumsq += v * v;
+        }
+    st.samples = g->crop_w * g->crop_h;
+    return st;
+}
+
+// The picture-score operation: honest sums over the rectangle of the coded planes the batch buffer holds.
+std::atomic<int> g_stats_calls{0};
+int stub_luma_stats(DevCtx *, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const uint8_t *d_yuv_coded, int n,
+                    mvhp_luma_stats_t *d_stats, float *ms, std::string &err)
+{
+    g_stats_calls++;
+    if (!p || !g || !d_yuv_coded || !d_stats || n <= 0 || g->crop_w == 0 || g->crop_h == 0 || g->crop_x + g->crop_w > p->width_mbs * 16 ||
+        g->crop_y + g->crop_h > p->height_mbs * 16) { err = "stub: picture-score launch without buffers or rectangle"; return MVHP_FAILURE; }
+    const size_t yb = mvhp_yuv_frame_bytes(p), Wp = (size_t)p->width_mbs * 16;
+    for (int i = 0; i < n; i++) {
+        mvhp_luma_stats_t st{};
+        const uint8_t *pic = d_yuv_coded + (size_t)i * yb;
+        for (uint32_t y = g->crop_y; y < g->crop_y + g->crop_h; y++)
+            for (uint32_t x = g->crop_x; x < g->crop_x + g->crop_w; x++) {
+                const uint64_t v = pic[(size_t)y * Wp + x];
+                st.sum += v;
+                st.sumsq += v * v;
+            }
+        st.samples = g->crop_w * g->crop_h;
+        d_stats[i] = st;
+    }
+    if (ms) *ms = 0.05f;
+    return MVHP_SUCCESS;
+}
+
 // The output-geometry operation: the coded planes are written in full (the scratch buffer must hold them), every output
 // picture is filled up to its last byte (the output buffers must hold n pictures of the geometry) and stamped: planes
 // 0x5a, checksum of the records in bytes 0-7, 0x77 in the last byte; RGB 0xa5, the checksum in bytes 8-15, 0x78 last.
@@ -134,9 +185,9 @@ int stub_recon_geometry(DevCtx *, const mvhp_stream_params_t *p, const mvhp_outp
     const size_t gy = mvhp_geometry_yuv_bytes(g), gr = mvhp_geometry_rgb_bytes(g);
     for (int i = 0; i < n; i++)
         expand_compact((const uint8_t *)d_compact + (size_t)i * stride, (size_t)p->width_mbs * p->height_mbs, (uint8_t *)d_packed + (size_t)i * pb);
-    memset(d_yuv_coded, 0x11, (size_t)n * yb);
     for (int i = 0; i < n; i++) {
         const uint64_t h = checksum((const uint8_t *)d_packed + (size_t)i * pb, pb);
+        fill_coded(d_yuv_coded + (size_t)i * yb, yb, h);
         if (d_yuv_out) {
             memset(d_yuv_out + (size_t)i * gy, 0x5a, gy);
             memcpy(d_yuv_out + (size_t)i * gy, &h, sizeof(h));
@@ -175,11 +226,11 @@ int stub_recon_jpeg(DevCtx *, const mvhp_stream_params_t *p, const mvhp_output_g
     if (cap != (size_t)n * gy) { err = "stub: the blob is not n raw pictures long"; return MVHP_FAILURE; }
     for (int i = 0; i < n; i++)
         expand_compact((const uint8_t *)d_compact + (size_t)i * stride, (size_t)p->width_mbs * p->height_mbs, (uint8_t *)d_packed + (size_t)i * pb);
-    memset(d_yuv_coded, 0x11, (size_t)n * yb);
     if (d_yuv_out) memset(d_yuv_out, 0x12, (size_t)n * gy);
     size_t pos = 0;
     for (int i = 0; i < n; i++) {
         const uint64_t h = checksum((const uint8_t *)d_packed + (size_t)i * pb, pb);
+        fill_coded(d_yuv_coded + (size_t)i * yb, yb, h);
         const size_t len = stub_jpeg_length(h, gy);
         mvhp_jpeg_entry_t e{pos, 0, MVHP_JPEG_TOO_BIG};
         if (!stub_jpeg_too_big(h) && pos + len <= cap) {
@@ -199,10 +250,10 @@ int stub_recon_jpeg(DevCtx *, const mvhp_stream_params_t *p, const mvhp_output_g
     return MVHP_SUCCESS;
 }
 
-const mvengine::DeviceApi g_stub = {stub_device_count, stub_host_alloc, stub_host_free, stub_ctx_create, stub_ctx_destroy,
+mvengine::DeviceApi g_stub = {stub_device_count, stub_host_alloc, stub_host_free, stub_ctx_create, stub_ctx_destroy,
                                     stub_dev_alloc, stub_dev_free, stub_dev_free_bytes, stub_copy_n, stub_copy_n, stub_recon,
                                     nullptr, nullptr,   // (no placed arena on the stub device)
-                                    stub_recon_geometry, stub_recon_jpeg};
+                                    stub_recon_geometry, stub_recon_jpeg, stub_luma_stats};
 
 uint64_t picture_checksum(const mvhp_stream &s, int idr)
 {
@@ -290,6 +341,57 @@ struct CheckJ {
         memcpy(&got, rgb, 8);
         if (got != h || rgb[8] != 0x3c || rgb[len - 1] != kLastJpeg) c.bad++;
         c.bytes += len;
+        c.ok++;
+        return 1;
+    }
+};
+
+// sink of the score mode: what CheckG and CheckJ check of the picture, and g->reserved[1] = the score of the stub's coded planes over
+// the geometry's rectangle
+struct CheckS {
+    const mvhp_stream *s = nullptr;
+    mvhp_output_request_t req{};   // without MVHP_OUTPUT_SCORE: what decides the geometry
+    int mask = 0;
+    int calls = 0, ok = 0, failed = 0, bad = 0, next_seq = 0, formed_n = 0, no_op = 0;
+    std::vector<int> order;
+    std::vector<uint32_t> scores;
+    static int sink(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                    const uint8_t *yuv, const uint8_t *rgb)
+    {
+        CheckS &c = *static_cast<CheckS *>(user);
+        c.calls++;
+        if (seq != c.next_seq || idr != c.order[(size_t)seq] || !g) c.bad++;
+        c.next_seq = seq + 1;
+        const bool jpeg = (c.mask & MVHP_OUT_JPEG) != 0;
+        mvhp_output_geometry_t want;
+        const bool formed = mvhp_output_geometry(c.s, idr, &c.req, &want) == MVHP_SUCCESS;
+        if (formed) c.formed_n++;
+        const uint64_t h = picture_checksum(*c.s, idr);
+        if (rc != MVHP_SUCCESS) {
+            c.failed++;
+            if (err && strstr(err, "picture-score operation")) c.no_op++;
+            else if (!err || !*err || yuv || rgb || (formed && !(jpeg && stub_jpeg_too_big(h)))) c.bad++;
+            return 0;
+        }
+        if (!formed) { c.bad++; return 0; }
+        const bool coded = want.crop_x == 0 && want.crop_y == 0 && want.out_w == p->width_mbs * 16 && want.out_h == p->height_mbs * 16 &&
+                           want.crop_w == want.out_w && want.crop_h == want.out_h;
+        const mvhp_luma_stats_t st = expected_stats(h, jpeg || !coded, p, &want);
+        want.reserved[1] = mvblank::luma_score(st.sum, st.sumsq, st.samples);
+        if (jpeg) want.reserved[0] = (uint32_t)stub_jpeg_length(h, mvhp_geometry_yuv_bytes(&want));
+        if (memcmp(&want, g, sizeof(want)) != 0) { c.bad++; return 0; }
+        c.scores.push_back(g->reserved[1]);
+        uint64_t got = 0;
+        if (jpeg) {
+            if (yuv || !rgb) { c.bad++; return 0; }
+            memcpy(&got, rgb, 8);
+            if (got != h || rgb[want.reserved[0] - 1] != kLastJpeg) c.bad++;
+        } else {
+            const bool want_rgb = (c.mask & 1) != 0, want_yuv = !want_rgb || (c.mask & 2) == 0;
+            if ((yuv != nullptr) != want_yuv || (rgb != nullptr) != want_rgb) { c.bad++; return 0; }
+            if (yuv) { memcpy(&got, yuv, 8); if (got != h || yuv[mvhp_geometry_yuv_bytes(g) - 1] != (coded ? 0x5a : kLastYuv)) c.bad++; }
+            if (rgb) { memcpy(&got, rgb + 8, 8); if (got != h || rgb[mvhp_geometry_rgb_bytes(g) - 1] != (coded ? 0xa5 : kLastRgb)) c.bad++; }
+        }
         c.ok++;
         return 1;
     }
@@ -852,6 +954,165 @@ int main(int argc, char **argv)
                 mvhp_engine_destroy(e);
             }
             printf("JPEG MODE DONE\n");
+        }
+        if (argc > 5 && !strcmp(argv[5], "score")) {   // ---- score mode: MVHP_OUTPUT_SCORE against the stub's picture-score operation ----
+            std::vector<int> order;
+            for (int k = 0; k < 3 * n3; k++) order.push_back(k % n3);
+            auto run_score = [&](const char *name, mvhp_engine_opts_t o, int mask, mvhp_output_request_t req, bool flag, CheckS &c,
+                                 mvhp_decode_stats_t &stats) {
+                mvhp_engine_t *e = nullptr;
+                if (mvhp_engine_create(&o, &e) != MVHP_SUCCESS) { failures++; return MVHP_FAILURE; }
+                c.s = &s3; c.req = req; c.order = order; c.mask = mask;
+                if (flag) req.flags |= MVHP_OUTPUT_SCORE;
+                const int rc = mvhp_engine_decode_ex(e, &s3, order.data(), (int)order.size(), (int)order.size(), mask, &req, CheckS::sink, &c, &stats);
+                mvhp_engine_destroy(e);
+                printf("%-28s rc=%d mask=%d flags=%u ok=%u failed=%u batches=%u geometry=%u requeued=%u d2h=%llu\n", name, rc, mask, req.flags,
+                       stats.pictures_ok, stats.pictures_failed, stats.batches, stats.geometry_launches, stats.batches_requeued,
+                       (unsigned long long)stats.d2h_bytes);
+                return rc;
+            };
+            int distinct_checked = 0;
+            for (int contexts = 1; contexts <= 3; contexts++)
+                for (int mask : {0, MVHP_OUT_RGB, MVHP_OUT_RGB_ONLY, MVHP_OUT_JPEG})
+                    for (mvhp_output_request_t req : {mvhp_output_request_t{0, 0, 0, 0}, crop, box}) {
+                        if (mask == MVHP_OUT_JPEG) req.reserved = MVHP_JPEG_REQUEST(80, 0);
+                        mvhp_engine_opts_t o = base; o.contexts = contexts; o.chunk_pictures = 2; o.batch_pictures = contexts == 1 ? 64 : 3;
+                        // without the flag: the sink's geometry has reserved[1] = 0 (CheckG / CheckJ compare all of it) and the
+                        // operation is never called
+                        mvhp_decode_stats_t st0;
+                        const int calls0 = g_stats_calls;
+                        if (mask == MVHP_OUT_JPEG) {
+                            CheckJ cj; cj.s = &s3; cj.req = req; cj.order = order;
+                            mvhp_engine_t *e = nullptr;
+                            EXPECT(mvhp_engine_create(&o, &e) == MVHP_SUCCESS);
+                            EXPECT(mvhp_engine_decode_ex(e, &s3, order.data(), (int)order.size(), (int)order.size(), mask, &req, CheckJ::sink, &cj, &st0) == MVHP_SUCCESS);
+                            mvhp_engine_destroy(e);
+                            EXPECT(cj.bad == 0);
+                        } else {
+                            CheckG cg;
+                            EXPECT(run_ex("score: flag off", o, s3, order, mask, req, cg, st0) == MVHP_SUCCESS);
+                            EXPECT(cg.bad == 0);
+                        }
+                        EXPECT(g_stats_calls == calls0);
+                        // with it (three contexts: the first batch of context 0 fails and is re-queued, and scored again)
+                        o.fail_context = contexts == 3 ? 0 : -1;
+                        CheckS c; mvhp_decode_stats_t st;
+                        EXPECT(run_score(req.flags & MVHP_OUTPUT_BOX ? "score box" : req.flags ? "score crop" : "score coded size", o, mask, req,
+                                         true, c, st) == MVHP_SUCCESS);
+                        EXPECT(c.bad == 0 && c.no_op == 0 && c.calls == (int)order.size() && c.ok == (int)st.pictures_ok && c.ok + c.failed == c.calls);
+                        EXPECT(c.ok == (int)st0.pictures_ok);
+                        EXPECT(st.d2h_bytes == st0.d2h_bytes + 32ull * (uint64_t)c.formed_n);   // exactly one record per picture of a batch
+                        EXPECT((int)st.batches_requeued == (contexts == 3 ? 1 : 0));
+                        EXPECT(g_stats_calls - calls0 == (int)st.batches);   // one call behind every launch that succeeded
+                        if (!req.flags) EXPECT(st.geometry_launches == 0);   // the flag alone: still the coded-size path
+                        std::vector<uint32_t> d = c.scores;
+                        std::sort(d.begin(), d.end());
+                        if (std::unique(d.begin(), d.end()) - d.begin() >= 3) distinct_checked++;
+                    }
+            // The scores tell pictures apart in 27 of the 36 runs: there the stub's planes are the picture's repeated checksum.  In the
+            // 9 coded-size runs without JPEG its planes are 0x5a past their first 8 bytes, and the scores of pictures nearly agree.
+            EXPECT(distinct_checked >= 27);
+            {   // a device table without the operation: every picture of the call fails with the message
+                g_stub.luma_stats = nullptr;
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 4;
+                CheckS c; mvhp_decode_stats_t st;
+                const int calls0 = g_stats_calls, recon0 = g_recon_calls + g_geometry_calls + g_jpeg_calls;
+                EXPECT(run_score("score: table without it", o, 0, crop, true, c, st) == MVHP_FAILURE);
+                EXPECT(c.bad == 0 && c.ok == 0 && c.no_op == c.formed_n && c.no_op > 0 && g_stats_calls == calls0);
+                EXPECT(g_recon_calls + g_geometry_calls + g_jpeg_calls == recon0);
+                CheckG cg;   // ... and a call without the flag is not affected
+                EXPECT(run_ex("score: table without it, off", o, s3, order, 0, crop, cg, st) == MVHP_SUCCESS && cg.bad == 0);
+                g_stub.luma_stats = stub_luma_stats;
+            }
+            {   // minivideo_decode under MINIVIDEO_SKIP_BLANK=1 on the stub device: two engine calls on one engine, the second one's
+                // files written over the first one's.  With the threshold at its maximum every stub picture is blank, so each slot
+                // with alternates ends on the highest score among its candidates; the files start with the records' checksum.
+                char tmpl[] = "/tmp/mvharness_XXXXXX";
+                const char *dir = mkdtemp(tmpl);
+                char cwd[4096];
+                EXPECT(dir != nullptr && getcwd(cwd, sizeof(cwd)) != nullptr);
+                std::string in = argv[4];
+                if (in[0] != '/') in = std::string(cwd) + "/" + in;
+                EXPECT(dir && chdir(dir) == 0);
+                setenv("MINIVIDEO_SKIP_BLANK", "1", 1);
+                setenv("MINIVIDEO_BLANK_VARIANCE", "16256", 1);
+                setenv("MINIVIDEO_BLANK_ALTERNATES", "3", 1);
+                std::vector<uint32_t> sc((size_t)n3);
+                for (int idr = 0; idr < n3; idr++) {
+                    mvhp_stream_params_t p;
+                    mvhp_output_geometry_t g;
+                    EXPECT(mvhp_stream_params(&s3, idr, &p) == MVHP_SUCCESS && mvhp_output_geometry(&s3, idr, nullptr, &g) == MVHP_SUCCESS);
+                    const mvhp_luma_stats_t st = expected_stats(picture_checksum(s3, idr), false, &p, &g);
+                    sc[(size_t)idr] = mvblank::luma_score(st.sum, st.sumsq, st.samples);
+                }
+                int moved = 0;
+                for (int num : {1, 2, n3 - 2})
+                    for (const char *writers : {"2", "0"}) {
+                        setenv("MINIVIDEO_WRITERS", writers, 1);
+                        MediaFile_t *m = nullptr;
+                        EXPECT(minivideo_open(in.c_str(), &m) == SUCCESS);
+                        EXPECT(m && minivideo_parse(m, false, true, false) == SUCCESS);
+                        const int calls0 = g_stats_calls;
+                        EXPECT(m && minivideo_decode(m, ".", PICTURE_YUV420, 75, num, PICTURE_UNFILTERED) == SUCCESS);
+                        EXPECT(g_stats_calls > calls0);
+                        std::vector<int> slots;
+                        for (int k = 0; k < num; k++) slots.push_back(k);
+                        int good = 0;
+                        for (int k = 0; k < num; k++) {
+                            std::vector<int> cand{slots[(size_t)k]};
+                            for (int i : mvblank::alternates(slots, n3, 3, k)) cand.push_back(i);
+                            std::vector<uint32_t> v;
+                            for (int i : cand) v.push_back(sc[(size_t)i]);
+                            const int final_idr = cand[(size_t)mvblank::choose(v.data(), (int)v.size(), 16u * 16256u)];
+                            if (final_idr != slots[(size_t)k]) moved++;
+                            const std::string name = std::string(m->file_name) + (num > 1 ? "_" + std::to_string(k) : "") + ".yuv";
+                            const std::vector<uint8_t> f = read_file(name);
+                            remove(name.c_str());
+                            uint64_t got = 0;
+                            if (f.size() >= 8) memcpy(&got, f.data(), 8);
+                            if (got == picture_checksum(s3, final_idr)) good++;
+                        }
+                        printf("%-28s n=%d writers=%s right picture in %d files\n", "public API, blank pictures", num, writers, good);
+                        EXPECT(good == num);
+                        EXPECT(minivideo_close(&m) == SUCCESS);
+                    }
+                EXPECT(moved >= 1);   // (some slot did give way to an alternate)
+                unsetenv("MINIVIDEO_SKIP_BLANK"); unsetenv("MINIVIDEO_BLANK_VARIANCE"); unsetenv("MINIVIDEO_BLANK_ALTERNATES"); unsetenv("MINIVIDEO_WRITERS");
+                EXPECT(chdir(cwd) == 0);
+                rmdir(dir);
+            }
+            // malformed values of the three switches of minivideo_decode: FAILURE, with a message, before the device is touched
+            struct Bad { const char *var, *value; };
+            for (const Bad &b : {Bad{"MINIVIDEO_BLANK_VARIANCE", "abc"}, Bad{"MINIVIDEO_BLANK_VARIANCE", "-1"}, Bad{"MINIVIDEO_BLANK_VARIANCE", "16257"},
+                                 Bad{"MINIVIDEO_BLANK_ALTERNATES", "0"}, Bad{"MINIVIDEO_BLANK_ALTERNATES", "17"}, Bad{"MINIVIDEO_SKIP_BLANK", "yes"}}) {
+                setenv("MINIVIDEO_SKIP_BLANK", "1", 1);
+                setenv(b.var, b.value, 1);
+                MediaFile_t *m = nullptr;
+                EXPECT(minivideo_open(argv[4], &m) == SUCCESS);
+                EXPECT(m && minivideo_parse(m, false, true, false) == SUCCESS);
+                const int ctx_before = g_ctx_created, launches_before = g_recon_calls + g_geometry_calls + g_stats_calls;
+                fflush(stdout);
+                fflush(stderr);
+                int pipefd[2];
+                EXPECT(pipe(pipefd) == 0);
+                const int saved = dup(2);
+                dup2(pipefd[1], 2);
+                const int rc = m ? minivideo_decode(m, ".", PICTURE_YUV420, 75, n3, PICTURE_UNFILTERED) : SUCCESS;
+                fflush(stderr);
+                dup2(saved, 2);
+                close(saved);
+                close(pipefd[1]);
+                char msg[512] = "";
+                const ssize_t got = read(pipefd[0], msg, sizeof(msg) - 1);
+                close(pipefd[0]);
+                printf("%-28s %s='%s' rc=%d message: %s", "malformed blank switch", b.var, b.value, rc, got > 0 ? msg : "(none)\n");
+                EXPECT(rc == FAILURE && got > 0 && strstr(msg, b.var) != nullptr);
+                EXPECT(g_ctx_created == ctx_before && g_recon_calls + g_geometry_calls + g_stats_calls == launches_before);
+                EXPECT(minivideo_close(&m) == SUCCESS);
+                unsetenv(b.var);
+            }
+            unsetenv("MINIVIDEO_SKIP_BLANK");
+            printf("SCORE MODE DONE\n");
         }
     }
     EXPECT(g_live_ctx == 0 && g_dev_allocs == 0);
