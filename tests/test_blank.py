@@ -205,3 +205,17 @@ def test_malformed_values_fail_the_call_before_any_device_work(tmp_path, var, ba
     assert var in r.stderr and "'%s'" % bad in r.stderr and "decode did not succeed" in r.stderr, r.stdout + r.stderr
     assert "hip" not in r.stderr.lower() and "device" not in r.stderr.lower(), r.stderr
     assert sorted(os.listdir(tmp_path)) == ["c.264"]
+
+
+def test_tiled_reference_of_the_split_launch_test():
+    """tests/test_gpu_launch_splits.py computes the records of 4099 base pictures and tiles them: the same bytes as the direct
+    reference on the first 300 pictures and across the wrap; 16 one-row bands put one picture more than a launch holds at
+    524 289"""
+    from tests import test_gpu_launch_splits as X
+    base, rec = X.stats_case()
+    n = X.STATS_CYCLE + 11
+    yuv, want = X.tiled(base, n, X.STATS_CYCLE), X.tiled(rec, n, X.STATS_CYCLE)
+    assert L.records(yuv[:300], 300, 1, 1, X.STATS_RECT).tobytes() == want[:300].tobytes()
+    assert L.records(yuv[-30:], 30, 1, 1, X.STATS_RECT).tobytes() == want[-30:].tobytes()
+    assert len({r.tobytes() for r in rec}) == X.STATS_CYCLE
+    assert X.STATS_RECT[3] * X.STATS_PER_LAUNCH == 1 << 23

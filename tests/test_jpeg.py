@@ -1,14 +1,15 @@
 """CPU: the JPEG stream format and arithmetic as tests/jpeg_ref.py states them (the GPU tests pin the kernels to that model byte
 for byte): the quantisation tables of the library, the model against its own entropy decoder, against the exact transform, and
-against libjpeg-turbo inside PIL."""
+against libjpeg-turbo inside PIL; and that the cases of tests/test_gpu_jpeg_extents.py are what they claim to be."""
 import io
+import re
 
 import numpy as np
 import pytest
 from PIL import Image
 
 from minivideo_amd import hotpath
-from tests import jpeg_ref as J
+from tests import jpeg_ref as J, test_gpu_jpeg_extents as X
 
 QUALITIES = (1, 50, 75, 100)
 # the inputs of the accuracy checks: the GPU tests' content (tests/jpeg_ref.py content(): flat, single-coefficient, sparse and
@@ -131,3 +132,50 @@ def test_huffman_tables_are_those_of_libjpeg():
         return out
 
     assert dht(J.header(16, 16, 50, 1)) == dht(theirs) and len(dht(theirs)) == 4
+
+
+@pytest.mark.parametrize("w,h,restart,quality,intervals", X.INTERVAL_CASES + X.WIDE_CASES)
+def test_extent_cases_have_their_interval_counts(w, h, restart, quality, intervals):
+    """the model's file holds that many restart intervals (RSTm markers + 1: a 0xFF of the entropy-coded bytes is followed by
+    0x00), and the API accepts the picture"""
+    body = J.model_file(w, h, X.SEED, quality, restart)[J.HEADER_BYTES:]
+    assert len(re.findall(rb"\xff[\xd0-\xd7]", body)) + 1 == intervals and body.endswith(b"\xff\xd9")
+    assert w % 2 == 0 and h % 2 == 0 and 2 <= min(w, h) and max(w, h) <= 65534 and w * h <= 1 << 28
+
+
+def test_extent_cases_straddle_the_chunks():
+    counts = sorted(c[4] for c in X.INTERVAL_CASES)
+    assert counts[0] == X.SCAN_CHUNK and counts[1] == X.SCAN_CHUNK + 1 and {4 * X.SCAN_CHUNK - 1, 4 * X.SCAN_CHUNK} <= set(counts)
+    assert counts[-1] == 16 * X.SCAN_CHUNK
+    assert X.BATCH_COUNTS[:2] == (X.PLACE_CHUNK, X.PLACE_CHUNK + 1) and X.BATCH_COUNTS[2] > 2 * X.PLACE_CHUNK
+
+
+def test_batch_cycle_and_capacity_layout():
+    """61 pictures of more than 30 lengths; under the chosen capacity the layout rule refuses exactly picture 2098, the noise
+    picture in the third placement chunk, and with one byte less also the last one"""
+    _, files = X.batch_pictures(X.BATCH_CYCLE)
+    assert len({len(f) for f in files}) > 30
+    _, files, cap = X.capacity_batch()
+    assert len(files) == 2100 and X.BATCH_NOISE[1] > 2 * X.PLACE_CHUNK > X.BATCH_NOISE[0] > X.PLACE_CHUNK
+    lens = [len(f) for f in files]
+    assert lens[2098] > lens[2099] and lens[1500] > max(lens[:X.BATCH_CYCLE])
+    for c, failed in ((cap, [2098]), (cap - 1, [2098, 2099])):
+        lay = J.blob_layout(lens, c)
+        assert [k for k, e in enumerate(lay) if e[2] == J.STATUS_TOO_BIG] == failed
+        assert all(e[0] + e[1] <= c for e in lay)
+    assert J.blob_layout(lens, cap)[2099][0] + lens[2099] == cap
+
+
+def test_sign_blocks_reach_the_transforms_bound():
+    """max |z| beyond 2^30 and within the bound the 32-bit argument rests on; DC levels reach -1024; AC levels stay within the
+    +-1023 of the baseline categories (1020, three below)"""
+    yuv = X.sign_blocks()
+    zmax, ac, dc_lo, dc_hi = X.sign_block_figures(yuv)
+    assert (zmax, ac, dc_lo, dc_hi) == (1073883168, 1020, -1024, 1016)
+    assert 1 << 30 < zmax <= 46344 * 23173 and zmax + (255 << 19) < 1 << 31
+    lv = J.quantised(yuv, 128, 64, 100)
+    at = {divmod(int(J.ZIGZAG[k]), 8) for k in range(1, 64) if np.abs(lv[:, :, k]).max() == ac}
+    assert (0, 4) in at
+    for quality in (1, 50, 100):
+        d = J.decode_levels(J.encode(yuv, 128, 64, quality))
+        assert np.array_equal(d["levels"], J.quantised(yuv, 128, 64, quality))

@@ -236,3 +236,19 @@ def test_default_mode_ignores_the_crop_like_the_reference(fmt):
         else:
             px, w, h = refdec.read_bmp(files[k])
             assert (w, h) == (16 * W, 16 * H) and np.array_equal(px, rgb)
+
+
+@pytest.mark.parametrize("mode", ["crop_copy", "resample", "resample_1to1"])
+def test_tiled_reference_of_the_split_launch_tests(mode):
+    """tests/test_gpu_launch_splits.py computes the reference on 263 base pictures and tiles it: the same bytes as the direct
+    reference on the first 300 pictures"""
+    from tests import test_gpu_launch_splits as X
+    g = X.MODES[mode][0]
+    ow, oh = g[4:] if len(g) == 6 else g[2:4]
+    base, want, want_rgb = X.resample_case(mode)
+    yuv = X.tiled(base, 300, X.RESAMPLE_CYCLE)
+    assert np.array_equal(yuv[X.RESAMPLE_CYCLE:], base[:300 - X.RESAMPLE_CYCLE]) and len({p.tobytes() for p in base}) == X.RESAMPLE_CYCLE
+    direct = R.resample(yuv, 1, 1, g[:4] + (ow, oh))
+    assert np.array_equal(direct, X.tiled(want, 300, X.RESAMPLE_CYCLE))
+    assert np.array_equal(R.to_rgb(direct, ow, oh), X.tiled(want_rgb, 300, X.RESAMPLE_CYCLE))
+    assert len({p.tobytes() for p in want}) == X.RESAMPLE_CYCLE        # a repeated or misplaced picture changes bytes
