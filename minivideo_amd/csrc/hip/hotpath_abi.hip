@@ -771,90 +771,46 @@ int eng_d2h(DevCtx *d, int n, void *const *dst, const void *const *src, const si
     return eng_copy_all(d, d->down, d->ev[4], d->ev[5], hipMemcpyDeviceToHost, n, dst, src, bytes, ms, err);
 }
 
-// g == NULL: planes (+ RGB into d_rgb) of the coded size.  Otherwise: planes of the coded size into d_yuv without the fused
-// colour epilogue, the deblocking filter when p asks for it, then the output-geometry pass into out_yuv / out_rgb.
-// j != NULL: planes only, as for a geometry, and the JPEG encoder behind them (on out_yuv when g is given, else on d_yuv).
-struct JpegOut {
-    const mvhp_jpeg_params_t     *params;
-    const mvhp_output_geometry_t *geom;    // of the pictures that are coded
-    uint8_t                      *blob;
-    size_t                        cap;
-    mvhp_jpeg_entry_t            *table;
-};
-
-int eng_recon_impl(DevCtx *d, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const void *d_compact, size_t stride,
-                   void *d_packed, int n, uint8_t *d_yuv, uint8_t *d_rgb, uint8_t *out_yuv, uint8_t *out_rgb, float *ms, int *layout,
-                   int *waves, std::string &err, const JpegOut *j = nullptr)
+// One batch, on the context's stream inside one pair of events: expand, reconstruction (planes only when a resample pass or the
+// encoder follows, otherwise with fused RGB into d_rgb), the resample pass, the encoder, the picture scores; then one wait and one
+// read of the error word.  (When the word is set the scores of that batch have been computed already: nothing reads them.)
+int eng_run_batch(DevCtx *d, const mvengine::BatchJob &j, mvengine::BatchDone &done, std::string &err)
 {
     mvhp_ctx *c = d->c;
-    if (!params_ok(p) || !d_compact || !d_packed || !d_yuv || n <= 0) { err = "reconstruction: invalid argument"; return MVHP_FAILURE; }
+    const mvhp_stream_params_t *p = j.params;
+    const bool resample = j.out_yuv || j.out_rgb;
+    if (!params_ok(p) || !j.d_compact || !j.d_packed || !j.d_yuv || j.n <= 0) { err = "reconstruction: invalid argument"; return MVHP_FAILURE; }
+    if ((resample || j.jpeg) && !j.geom) { err = "reconstruction: no output geometry"; return MVHP_FAILURE; }
+    if (j.jpeg && (!j.blob || !j.table || j.out_rgb)) { err = "reconstruction: invalid JPEG output"; return MVHP_FAILURE; }
+    if (j.geom && !resample && !j.jpeg) { err = "reconstruction: an output geometry without an output buffer"; return MVHP_FAILURE; }
     ENG_TRY(hipSetDevice(c->device));
     ENG_TRY(hipEventRecord(d->ev[2], c->stream));
-    if (mvhp_expand_compact_dev(c, p, d_compact, stride, n, d_packed, c->stream) != MVHP_SUCCESS) { err = mvhp_last_error(); return MVHP_FAILURE; }
+    if (mvhp_expand_compact_dev(c, p, j.d_compact, j.stride, j.n, j.d_packed, c->stream) != MVHP_SUCCESS) { err = mvhp_last_error(); return MVHP_FAILURE; }
     const bool deblock = (p->flags & MVHP_PARAM_DEBLOCK) != 0;
-    int rc = (g || j) ? launch_all(c, p, d_packed, n, d_yuv, nullptr, c->stream, true, false, deblock)
-               : launch_all(c, p, d_packed, n, d_yuv, d_rgb, c->stream, true, true, deblock);
+    int rc = (resample || j.jpeg) ? launch_all(c, p, j.d_packed, j.n, j.d_yuv, nullptr, c->stream, true, false, deblock)
+                                  : launch_all(c, p, j.d_packed, j.n, j.d_yuv, j.d_rgb, c->stream, true, true, deblock);
+    if (rc == MVHP_SUCCESS && resample) rc = mvhp_resample_dev(c, p, j.geom, j.d_yuv, j.n, j.out_yuv, j.out_rgb, c->stream);
+    if (rc == MVHP_SUCCESS && j.jpeg)
+        rc = mvhp_jpeg_encode_dev(c, j.geom, j.jpeg, resample ? j.out_yuv : j.d_yuv, j.n, j.blob, j.blob_cap, j.table, c->stream);
+    if (rc == MVHP_SUCCESS && j.stats) {
+        mvhp_output_geometry_t whole{};   // (no geometry: the rectangle is the coded picture)
+        whole.crop_w = whole.out_w = p->width_mbs * 16;
+        whole.crop_h = whole.out_h = p->height_mbs * 16;
+        rc = mvhp_luma_stats_dev(c, p, j.geom ? j.geom : &whole, j.d_yuv, j.n, j.stats, c->stream);
+    }
     if (rc != MVHP_SUCCESS) { err = mvhp_last_error(); return rc; }
-    if (g) {
-        rc = mvhp_resample_dev(c, p, g, d_yuv, n, out_yuv, out_rgb, c->stream);
-        if (rc != MVHP_SUCCESS) { err = mvhp_last_error(); return rc; }
-    }
-    if (j) {
-        rc = mvhp_jpeg_encode_dev(c, j->geom, j->params, g ? out_yuv : d_yuv, n, j->blob, j->cap, j->table, c->stream);
-        if (rc != MVHP_SUCCESS) { err = mvhp_last_error(); return rc; }
-    }
     ENG_TRY(hipEventRecord(d->ev[3], c->stream));
     std::string ew;
     ENG_TRY(hipEventSynchronize(d->ev[3]));   // (sleeps: blocking-sync event)
     ENG_TRY(read_err_word(c, c->stream, false, ew));
-    if (ms) ENG_TRY(hipEventElapsedTime(ms, d->ev[2], d->ev[3]));
-    if (layout) *layout = c->last_layout;
-    if (waves) *waves = c->last_waves;
+    ENG_TRY(hipEventElapsedTime(&done.ms, d->ev[2], d->ev[3]));
+    done.layout = c->last_layout;
+    done.waves = c->last_waves;
     if (!ew.empty()) {
         (void)hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), c->stream);
         err = ew;
         return MVHP_FAILURE;
     }
-    return MVHP_SUCCESS;
-}
-
-int eng_recon(DevCtx *d, const mvhp_stream_params_t *p, const void *d_compact, size_t stride, void *d_packed, int n, uint8_t *d_yuv,
-              uint8_t *d_rgb, float *ms, int *layout, int *waves, std::string &err)
-{
-    return eng_recon_impl(d, p, nullptr, d_compact, stride, d_packed, n, d_yuv, d_rgb, nullptr, nullptr, ms, layout, waves, err);
-}
-
-int eng_recon_geometry(DevCtx *d, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const void *d_compact, size_t stride,
-                       void *d_packed, int n, uint8_t *d_yuv_coded, uint8_t *d_yuv_out, uint8_t *d_rgb_out, float *ms, int *layout,
-                       int *waves, std::string &err)
-{
-    if (!g) { err = "reconstruction: no output geometry"; return MVHP_FAILURE; }
-    return eng_recon_impl(d, p, g, d_compact, stride, d_packed, n, d_yuv_coded, nullptr, d_yuv_out, d_rgb_out, ms, layout, waves, err);
-}
-
-int eng_recon_jpeg(DevCtx *d, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, int resample,
-                   const mvhp_jpeg_params_t *jp, const void *d_compact, size_t stride, void *d_packed, int n, uint8_t *d_yuv_coded,
-                   uint8_t *d_yuv_out, uint8_t *d_blob, size_t cap_bytes, mvhp_jpeg_entry_t *d_table, float *ms, int *layout,
-                   int *waves, std::string &err)
-{
-    if (!g || !jp || !d_blob || !d_table || (resample && !d_yuv_out)) { err = "reconstruction: invalid JPEG output"; return MVHP_FAILURE; }
-    const JpegOut j = {jp, g, d_blob, cap_bytes, d_table};
-    return eng_recon_impl(d, p, resample ? g : nullptr, d_compact, stride, d_packed, n, d_yuv_coded, nullptr, d_yuv_out, nullptr, ms,
-                          layout, waves, err, &j);
-}
-
-// the picture scores of a batch: mvhp_luma_stats_dev on the coded planes the reconstruction left in d_yuv_coded, on the context's
-// stream behind it; returns when the records are written
-int eng_luma_stats(DevCtx *d, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const uint8_t *d_yuv_coded, int n,
-                   mvhp_luma_stats_t *d_stats, float *ms, std::string &err)
-{
-    mvhp_ctx *c = d->c;
-    ENG_TRY(hipSetDevice(c->device));
-    ENG_TRY(hipEventRecord(d->ev[2], c->stream));
-    if (mvhp_luma_stats_dev(c, p, g, d_yuv_coded, n, d_stats, c->stream) != MVHP_SUCCESS) { err = mvhp_last_error(); return MVHP_FAILURE; }
-    ENG_TRY(hipEventRecord(d->ev[3], c->stream));
-    ENG_TRY(hipEventSynchronize(d->ev[3]));
-    if (ms) ENG_TRY(hipEventElapsedTime(ms, d->ev[2], d->ev[3]));
     return MVHP_SUCCESS;
 }
 
@@ -894,8 +850,8 @@ void eng_placed_free(DevCtx *d, void *arena)
 
 const mvengine::DeviceApi g_hip_api = {
     mvhp_device_count, mvhp_host_alloc, mvhp_host_free, eng_ctx_create, eng_ctx_destroy, eng_dev_alloc, eng_dev_free,
-    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_recon, eng_placed_alloc, eng_placed_free, eng_recon_geometry,
-    eng_recon_jpeg, eng_luma_stats,
+    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE,
+    eng_placed_alloc, eng_placed_free,
 };
 
 } // namespace

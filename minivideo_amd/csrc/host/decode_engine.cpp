@@ -132,28 +132,29 @@ struct PicResult {
     bool kept = false;       // the sink answered 2: its output chunk stays referenced until release_picture()
 };
 
+// The device buffers of a batch, one per kind.  The first four are what reconstruction itself needs and may be pieces of a placed
+// arena; the others are ordinary allocations always, also beside an arena: they are the small side of a batch that has them.
+enum BufKind {
+    kCompact,    // uploaded compact pictures, slot stride as in the chunks
+    kPacked,     // the records they expand to
+    kYuv,        // planes of the coded size: the output, or the input of the passes behind reconstruction
+    kRgb,        // fused RGB of the coded size
+    kOutYuv,     // output pictures of a batch with a geometry (what is downloaded then)
+    kOutRgb,
+    kJpegBlob,   // MVHP_OUT_JPEG: the encoder's blob (n x the raw picture) ...
+    kJpegTab,    // ... and table of a batch
+    kStats,      // MVHP_OUTPUT_SCORE: the records of a batch (n x 32 bytes)
+    kBufKinds,
+    kArenaKinds = kOutYuv,
+};
+
 struct DevBuf {
-    void *compact = nullptr; // uploaded compact pictures, slot stride as in the chunks
-    void *packed = nullptr;  // the records they expand to
-    uint8_t *yuv = nullptr, *rgb = nullptr;
-    size_t compact_cap = 0, packed_cap = 0, yuv_cap = 0, rgb_cap = 0;
+    struct { uint8_t *p = nullptr; size_t cap = 0; } m[kBufKinds];
     bool busy = false;
-    bool arena_piece = false;   // the four buffers are pieces of the context's placed arena: never freed one by one
-    // output pictures of a batch with a geometry (what is downloaded then; yuv above is the pass's input).  Ordinary
-    // allocations always, also beside a placed arena: they are the small side of such a batch.
-    uint8_t *out_yuv = nullptr, *out_rgb = nullptr;
-    size_t out_yuv_cap = 0, out_rgb_cap = 0;
-    // MVHP_OUT_JPEG: the encoder's blob (n x the raw picture) and table of a batch
-    uint8_t *jpeg_blob = nullptr, *jpeg_tab = nullptr;
-    size_t jpeg_blob_cap = 0, jpeg_tab_cap = 0;
-    // MVHP_OUTPUT_SCORE: the records of a batch (n x 32 bytes)
-    uint8_t *stats = nullptr;
-    size_t stats_cap = 0;
+    bool arena_piece = false;   // the first four buffers are pieces of the context's placed arena: never freed one by one
     void leave_arena()          // the four arena pieces are forgotten (they go with the arena); the output buffers stay
     {
-        compact = packed = nullptr;
-        yuv = rgb = nullptr;
-        compact_cap = packed_cap = yuv_cap = rgb_cap = 0;
+        for (int k = 0; k < kArenaKinds; k++) m[k] = {};
         arena_piece = false;
     }
 };
@@ -173,11 +174,54 @@ size_t write_empty_compact(uint8_t *buf, size_t mbs)
     return mbs * 4 + MVHP_MB_HEADER_BYTES;
 }
 
+// which outputs a call delivers
+struct Wants {
+    bool yuv = true, rgb = false;   // which of them are downloaded (the planes are always reconstructed)
+    bool jpeg = false;              // MVHP_OUT_JPEG: neither of them; JPEG files made on the device
+    bool score = false;             // MVHP_OUTPUT_SCORE (it changes no picture and no path)
+};
+// what a placed arena and the job's largest batch are planned for: pictures of the coded size, planes and RGB
+constexpr Wants kPlanesAndRgb = {true, true, false, false};
+
+// Device bytes per picture of one kind, for a batch of these parameters and this geometry (use_geom: it differs from the coded
+// size) in a call with these outputs; 0 = such a batch has no buffer of the kind.  The only place where the size of a batch
+// buffer is written: the allocations, the memory budget, the launch and the download all read it.
+size_t picture_bytes(BufKind k, const mvhp_stream_params_t &p, const mvhp_output_geometry_t &g, bool use_geom, const Wants &w)
+{
+    switch (k) {
+    case kCompact:  return compact_slot_bytes(p);
+    case kPacked:   return mvhp_packed_frame_bytes(&p);
+    case kYuv:      return mvhp_yuv_frame_bytes(&p);
+    case kRgb:      return w.rgb && !use_geom ? mvhp_rgb_frame_bytes(&p) : 0;
+    case kOutYuv:   return use_geom && (w.yuv || w.jpeg) ? mvhp_geometry_yuv_bytes(&g) : 0;
+    case kOutRgb:   return use_geom && w.rgb ? mvhp_geometry_rgb_bytes(&g) : 0;
+    case kJpegBlob: return w.jpeg ? mvhp_geometry_yuv_bytes(&g) : 0;
+    case kJpegTab:  return w.jpeg ? sizeof(mvhp_jpeg_entry_t) : 0;
+    case kStats:    return w.score ? sizeof(mvhp_luma_stats_t) : 0;
+    default:        return 0;
+    }
+}
+
+// all of them, and the one term that is no batch buffer: the JPEG encoder's scratch, which lives in the context.  136 bytes per
+// 8x8 block = 2.125 x the planes padded to whole MCUs; with the blob, 1 x the planes, that is 3.125 x, budgeted as 4.25 x for
+// that padding on small pictures -- the scratch's share is what the blob and the table entry leave of it
+size_t batch_picture_bytes(const mvhp_stream_params_t &p, const mvhp_output_geometry_t &g, bool use_geom, const Wants &w)
+{
+    size_t sum = 0;
+    for (int k = 0; k < kBufKinds; k++) sum += picture_bytes((BufKind)k, p, g, use_geom, w);
+    if (w.jpeg) sum += mvhp_geometry_yuv_bytes(&g) * 17 / 4 - mvhp_geometry_yuv_bytes(&g) - sizeof(mvhp_jpeg_entry_t);
+    return sum;
+}
+
+// where the pictures of a batch are downloaded from: the resample targets of a batch with a geometry, else the coded size
+BufKind planes_kind(bool use_geom) { return use_geom ? kOutYuv : kYuv; }
+BufKind rgb_kind(bool use_geom) { return use_geom ? kOutRgb : kRgb; }
+
 struct Batch {
     int id = 0;
     mvhp_stream_params_t params{};
     mvhp_output_geometry_t geom{};   // of every picture of the batch
-    bool use_geom = false;           // geom differs from the coded size: the batch runs the device table's recon_geometry
+    bool use_geom = false;           // geom differs from the coded size: the batch has a resample pass
     std::vector<int> seqs;           // slot -> position in `order`
     int capacity = 0;                // planned pictures (device buffers are sized for it)
     int total = -1;                  // pictures, known once the closing chunk has been issued
@@ -253,12 +297,14 @@ public:
     void release_picture(int seq);   // any thread
 private:
     bool grow(Pinned &p, size_t need);   // no lock needed
-    int batch_capacity(const mvhp_stream_params_t &p, const mvhp_output_geometry_t *g, int remaining) const;
+    int launch_cap(size_t per_picture) const;
+    int batch_capacity(const mvhp_stream_params_t &p, const mvhp_output_geometry_t &g, bool use_geom, int remaining) const;
+    size_t need(const Batch &b, BufKind k) const { return picture_bytes(k, b.params, b.geom, b.use_geom, w_); }   // per picture; 0: not needed
     bool picture_geometry(int idr, const mvhp_stream_params_t &p, mvhp_output_geometry_t &g, bool &use, std::string &why) const;
     int planned_batch(int cap, int remaining, int batch_id) const;
     int chunk_pictures(const mvhp_stream_params_t &p) const;
+    bool grow_dev(Ctx &c, DevBuf &b, BufKind k, size_t bytes);                   // no lock needed
     bool ensure_devbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err);   // no lock needed
-    bool ensure_outbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err);   // no lock needed
 
     const DeviceApi &api_;
     mvhp_engine_opts_t opts_{};
@@ -274,10 +320,8 @@ private:
     const mvhp_stream *s_ = nullptr;
     const int *order_ = nullptr;
     int n_order_ = 0, wanted_ = 0;
-    bool want_rgb_ = false, want_yuv_ = true;   // which outputs are downloaded (the planes are always reconstructed)
-    bool want_jpeg_ = false;                    // MVHP_OUT_JPEG: neither of them; JPEG files made on the device are
+    Wants w_;                                   // (score: taken out of req_.flags)
     mvhp_jpeg_params_t jpeg_{};
-    bool score_ = false;                        // MVHP_OUTPUT_SCORE (taken out of req_.flags: it changes no picture and no path)
     mvhp_output_request_t req_{};               // flags 0: pictures of the coded size
     bool stop_ = false;
     bool sink_waiting_ = false;
@@ -315,17 +359,8 @@ Engine::~Engine()
             for (DevBuf &b : c.bufs) if (b.arena_piece) b.leave_arena();
             api_.placed_free(c.dev, c.arena);
         }
-        for (DevBuf &b : c.bufs) {
-            if (b.compact) api_.dev_free(c.dev, b.compact);
-            if (b.packed) api_.dev_free(c.dev, b.packed);
-            if (b.yuv) api_.dev_free(c.dev, b.yuv);
-            if (b.rgb) api_.dev_free(c.dev, b.rgb);
-            if (b.out_yuv) api_.dev_free(c.dev, b.out_yuv);
-            if (b.out_rgb) api_.dev_free(c.dev, b.out_rgb);
-            if (b.jpeg_blob) api_.dev_free(c.dev, b.jpeg_blob);
-            if (b.jpeg_tab) api_.dev_free(c.dev, b.jpeg_tab);
-            if (b.stats) api_.dev_free(c.dev, b.stats);
-        }
+        for (DevBuf &b : c.bufs)
+            for (auto &m : b.m) if (m.p) api_.dev_free(c.dev, m.p);
         if (c.dev) api_.ctx_destroy(c.dev);
     }
 }
@@ -419,24 +454,22 @@ bool Engine::picture_geometry(int idr, const mvhp_stream_params_t &p, mvhp_outpu
     return true;
 }
 
-int Engine::batch_capacity(const mvhp_stream_params_t &p, const mvhp_output_geometry_t *g, int remaining) const
+// the most pictures a launch may hold, of pictures that take per_picture bytes of device memory each
+int Engine::launch_cap(size_t per_picture) const
 {
     const int n_ctx = (int)ctx_.size();
     // the cap: four pictures per CU (the four-picture kernel's full round); a long job -- from 4096 pictures per context on --
     // runs its steady state in launches of 2048, eight per CU, which is what the eight-picture kernel wants (round 3: the
     // product path reaches the kernel the bench times; the ramp and the taper stay as they are)
-    int cap = opts_.batch_pictures > 0 ? opts_.batch_pictures : ((n_order_ >= 4096 * n_ctx) ? 2048 : 1024);
-    const size_t per_pic = compact_slot_bytes(p) + mvhp_packed_frame_bytes(&p) + mvhp_yuv_frame_bytes(&p) +
-                           (g ? (want_yuv_ || want_jpeg_ ? mvhp_geometry_yuv_bytes(g) : 0) + (want_rgb_ ? mvhp_geometry_rgb_bytes(g) : 0)
-                              : (want_rgb_ ? mvhp_rgb_frame_bytes(&p) : 0)) +
-                           // (the blob, 1 x the planes, and the encoder's scratch in the context, 136 bytes per 8x8 block = 2.125 x the planes
-                           //  padded to whole MCUs: 3.125 x, budgeted as 4.25 x for that padding on small pictures)
-                           (want_jpeg_ ? (g ? mvhp_geometry_yuv_bytes(g) : mvhp_yuv_frame_bytes(&p)) * 17 / 4 : 0) +
-                           (score_ ? sizeof(mvhp_luma_stats_t) : 0);
+    const int cap = opts_.batch_pictures > 0 ? opts_.batch_pictures : ((n_order_ >= 4096 * n_ctx) ? 2048 : 1024);
     size_t budget = ctx_[0].mem_budget;
     for (const Ctx &c : ctx_) budget = std::min(budget, c.mem_budget);
-    const int mem_cap = (int)std::min<size_t>(1 << 20, std::max<size_t>(1, budget / std::max<size_t>(1, per_pic)));
-    cap = std::min(cap, mem_cap);
+    return std::min(cap, (int)std::min<size_t>(1 << 20, std::max<size_t>(1, budget / std::max<size_t>(1, per_picture))));
+}
+
+int Engine::batch_capacity(const mvhp_stream_params_t &p, const mvhp_output_geometry_t &g, bool use_geom, int remaining) const
+{
+    int cap = launch_cap(batch_picture_bytes(p, g, use_geom, w_));
     for (const Ctx &c : ctx_)
         if (c.arena && c.arena_pictures > 0 && same_params(c.arena_params, p)) cap = std::min(cap, c.arena_pictures);
     return planned_batch(cap, remaining, next_batch_id_);
@@ -471,8 +504,8 @@ bool Engine::ensure_devbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
     if (placed_ && api_.placed_alloc && !c.arena_tried) {
         c.arena_tried = true;
         const int n = std::max(bt.capacity, job_cap_);
-        const size_t bytes[4] = {(size_t)n * compact_slot_bytes(bt.params), (size_t)n * mvhp_packed_frame_bytes(&bt.params),
-                                 (size_t)n * mvhp_yuv_frame_bytes(&bt.params), (size_t)n * mvhp_rgb_frame_bytes(&bt.params)};
+        size_t bytes[kArenaKinds];
+        for (int i = 0; i < kArenaKinds; i++) bytes[i] = (size_t)n * picture_bytes((BufKind)i, bt.params, bt.geom, false, kPlanesAndRgb);
         void *ptrs[12];
         const double t0 = now_s();
         c.arena = api_.placed_alloc(c.dev, 3, bytes, ptrs);
@@ -497,90 +530,58 @@ bool Engine::ensure_devbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
             for (int k = 0; k < 3; k++) {
                 DevBuf &d = c.bufs[k];
                 // (ordinary buffers from an earlier call of another shape are released; none is in use: the first batch)
-                if (d.compact) api_.dev_free(c.dev, d.compact);
-                if (d.packed) api_.dev_free(c.dev, d.packed);
-                if (d.yuv) api_.dev_free(c.dev, d.yuv);
-                if (d.rgb) api_.dev_free(c.dev, d.rgb);
-                d.compact = ptrs[k * 4 + 0]; d.compact_cap = bytes[0];
-                d.packed = ptrs[k * 4 + 1]; d.packed_cap = bytes[1];
-                d.yuv = (uint8_t *)ptrs[k * 4 + 2]; d.yuv_cap = bytes[2];
-                d.rgb = (uint8_t *)ptrs[k * 4 + 3]; d.rgb_cap = bytes[3];
+                for (int i = 0; i < kArenaKinds; i++) {
+                    if (d.m[i].p) api_.dev_free(c.dev, d.m[i].p);
+                    d.m[i] = {(uint8_t *)ptrs[k * 4 + i], bytes[i]};
+                }
                 d.arena_piece = true;
             }
         }
     }
     if (b.arena_piece) {
-        const size_t n = (size_t)bt.capacity;
-        if (n * compact_slot_bytes(bt.params) <= b.compact_cap && n * mvhp_packed_frame_bytes(&bt.params) <= b.packed_cap &&
-            n * mvhp_yuv_frame_bytes(&bt.params) <= b.yuv_cap && n * mvhp_rgb_frame_bytes(&bt.params) <= b.rgb_cap)
-            return ensure_outbuf(c, b, bt, err);
+        bool fits = true;
+        for (int i = 0; i < kArenaKinds; i++)
+            fits = fits && (size_t)bt.capacity * picture_bytes((BufKind)i, bt.params, bt.geom, false, kPlanesAndRgb) <= b.m[i].cap;
         // a batch the arena was not sized for (another picture size, a later and longer job): this batch buffer leaves the
         // arena for ordinary allocations -- its pieces stay where they are until the engine goes (batch_capacity() keeps
         // batches of the arena's own shape inside it)
-        b.leave_arena();
+        if (!fits) b.leave_arena();
     }
-    auto need = [&](void **ptr, size_t *cap, size_t bytes) {
-        if (*cap >= bytes) return true;
-        const double t0 = now_s();
-        if (*ptr) api_.dev_free(c.dev, *ptr);
-        *ptr = api_.dev_alloc(c.dev, bytes);
-        *cap = *ptr ? bytes : 0;
-        {
-            std::lock_guard<std::mutex> l(alloc_mu_);
-            alloc_dev_s_ += now_s() - t0;
-            alloc_dev_bytes_ += bytes;
+    // The sizing rule is a property of the kind.  The first four are sized for the largest batch this call can form on a context,
+    // not for the batch at hand: the ramp and the taper hand a buffer batches of changing sizes, and every growth is a hipFree +
+    // hipMalloc in the middle of the pipeline (hipFree waits for the device) -- the second and third call of an engine still paid
+    // for that (0.55 s, then 0.51 s, same job).  The others -- output pictures of a geometry, JPEG blob and table, scores -- are
+    // sized for the batch at hand: geometries change inside a job, and these buffers are the small side of a batch.
+    static const struct { const char *of, *unit; } what[kBufKinds] = {
+        {"", " pictures"}, {"", " pictures"}, {"", " pictures"}, {"", " pictures"}, {"the output pictures of ", ""}, {"the output pictures of ", ""},
+        {"the JPEG files of ", ""}, {"the JPEG files of ", ""}, {"the picture scores of ", ""}};
+    const bool job_shape = bt.params.width_mbs == job_params_.width_mbs && bt.params.height_mbs == job_params_.height_mbs;
+    for (int k = 0; k < kBufKinds; k++) {
+        if (k < kArenaKinds && b.arena_piece) continue;   // (checked above; never grown one by one)
+        const size_t n = (size_t)std::max(bt.capacity, k < kArenaKinds && job_shape ? job_cap_ : 0);
+        if (!grow_dev(c, b, (BufKind)k, n * need(bt, (BufKind)k))) {
+            err = std::string("out of device memory for ") + what[k].of + "a batch of " + std::to_string(bt.capacity) + what[k].unit;
+            return false;
         }
-        return *ptr != nullptr;
-    };
-    // sized for the largest batch this call can form on a context, not for the batch at hand: the ramp and the taper hand a
-    // buffer batches of changing sizes, and every growth is a hipFree + hipMalloc in the middle of the pipeline (hipFree
-    // waits for the device) -- the second and third call of an engine still paid for that (0.55 s, then 0.51 s, same job)
-    const size_t n = (size_t)std::max(bt.capacity, (bt.params.width_mbs == job_params_.width_mbs && bt.params.height_mbs == job_params_.height_mbs) ? job_cap_ : 0);
-    if (!need(&b.compact, &b.compact_cap, n * compact_slot_bytes(bt.params)) ||
-        !need(&b.packed, &b.packed_cap, n * mvhp_packed_frame_bytes(&bt.params)) ||
-        !need((void **)&b.yuv, &b.yuv_cap, n * mvhp_yuv_frame_bytes(&bt.params)) ||
-        (want_rgb_ && !bt.use_geom && !need((void **)&b.rgb, &b.rgb_cap, n * mvhp_rgb_frame_bytes(&bt.params)))) {
-        err = "out of device memory for a batch of " + std::to_string(bt.capacity) + " pictures";
-        return false;
-    }
-    return ensure_outbuf(c, b, bt, err);
-}
-
-// the output pictures of a batch with a geometry: n x mvhp_geometry_{yuv,rgb}_bytes, sized for the batch at hand (geometries
-// change inside a job; these buffers are the small side of a batch)
-bool Engine::ensure_outbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
-{
-    if (!bt.use_geom && !want_jpeg_ && !score_) return true;
-    const size_t n = (size_t)bt.capacity;
-    auto need = [&](uint8_t **ptr, size_t *cap, size_t bytes) {
-        if (*cap >= bytes) return true;
-        const double t0 = now_s();
-        if (*ptr) api_.dev_free(c.dev, *ptr);
-        *ptr = (uint8_t *)api_.dev_alloc(c.dev, bytes);
-        *cap = *ptr ? bytes : 0;
-        {
-            std::lock_guard<std::mutex> l(alloc_mu_);
-            alloc_dev_s_ += now_s() - t0;
-            alloc_dev_bytes_ += bytes;
-        }
-        return *ptr != nullptr;
-    };
-    if (score_ && !need(&b.stats, &b.stats_cap, n * sizeof(mvhp_luma_stats_t))) {
-        err = "out of device memory for the picture scores of a batch of " + std::to_string(bt.capacity);
-        return false;
-    }
-    if (want_jpeg_ && (!need(&b.jpeg_blob, &b.jpeg_blob_cap, n * mvhp_geometry_yuv_bytes(&bt.geom)) ||
-                       !need(&b.jpeg_tab, &b.jpeg_tab_cap, n * sizeof(mvhp_jpeg_entry_t)))) {
-        err = "out of device memory for the JPEG files of a batch of " + std::to_string(bt.capacity);
-        return false;
-    }
-    if (!bt.use_geom) return true;
-    if (((want_yuv_ || want_jpeg_) && !need(&b.out_yuv, &b.out_yuv_cap, n * mvhp_geometry_yuv_bytes(&bt.geom))) ||
-        (want_rgb_ && !need(&b.out_rgb, &b.out_rgb_cap, n * mvhp_geometry_rgb_bytes(&bt.geom)))) {
-        err = "out of device memory for the output pictures of a batch of " + std::to_string(bt.capacity);
-        return false;
     }
     return true;
+}
+
+// allocate or grow one batch buffer (bytes 0: not needed, what it holds stays)
+bool Engine::grow_dev(Ctx &c, DevBuf &b, BufKind k, size_t bytes)
+{
+    auto &m = b.m[k];
+    if (m.cap >= bytes) return true;
+    const double t0 = now_s();
+    if (m.p) api_.dev_free(c.dev, m.p);
+    m.p = (uint8_t *)api_.dev_alloc(c.dev, bytes);
+    m.cap = m.p ? bytes : 0;
+    {
+        std::lock_guard<std::mutex> l(alloc_mu_);
+        alloc_dev_s_ += now_s() - t0;
+        alloc_dev_bytes_ += bytes;
+    }
+    return m.p != nullptr;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -659,7 +660,7 @@ void Engine::feeder()
             nb->params = p0;
             nb->geom = g0;
             nb->use_geom = use0;
-            nb->capacity = batch_capacity(p0, use0 ? &g0 : nullptr, avail);
+            nb->capacity = batch_capacity(p0, g0, use0, avail);
             nb->retry = rg != nullptr;
             nb->exclude_ctx = rg ? rg->exclude_ctx : -1;
             nb->seqs.reserve((size_t)nb->capacity);
@@ -899,7 +900,7 @@ void Engine::uploader(int k)
             std::vector<const void *> src((size_t)c->n);
             size_t bytes = 0;
             for (int i = 0; i < c->n; i++) {   // only what the entropy stage wrote crosses the link
-                dst[(size_t)i] = (uint8_t *)b->buf->compact + (size_t)(c->first_slot + i) * c->pic_bytes;
+                dst[(size_t)i] = b->buf->m[kCompact].p + (size_t)(c->first_slot + i) * c->pic_bytes;
                 src[(size_t)i] = c->buf.p + (size_t)i * c->pic_bytes;
                 bytes += c->used[(size_t)i];
             }
@@ -941,32 +942,35 @@ void Engine::launcher(int k)
             if (cx.fail_next) { cx.fail_next = false; inject = true; }
         }
         std::string err;
-        float ms = 0.f;
-        int layout = 0, waves = 0;
-        int rc = MVHP_SUCCESS;
+        BatchDone done{};
+        int rc = MVHP_FAILURE;
         const double t_call = now_s();
-        if (inject) { rc = MVHP_FAILURE; err = "injected failure (test hook)"; }
-        else if (score_ && !api_.luma_stats) { rc = MVHP_FAILURE; err = "this device table has no picture-score operation"; }
-        else if (want_jpeg_ && !api_.recon_jpeg) { rc = MVHP_FAILURE; err = "this device table has no JPEG operation"; }
-        else if (want_jpeg_)
-            rc = api_.recon_jpeg(cx.dev, &b->params, &b->geom, b->use_geom ? 1 : 0, &jpeg_, b->buf->compact,
-                                 compact_slot_bytes(b->params), b->buf->packed, b->total, b->buf->yuv,
-                                 b->use_geom ? b->buf->out_yuv : nullptr, b->buf->jpeg_blob,
-                                 (size_t)b->total * mvhp_geometry_yuv_bytes(&b->geom), (mvhp_jpeg_entry_t *)b->buf->jpeg_tab, &ms,
-                                 &layout, &waves, err);
-        else if (!b->use_geom)
-            rc = api_.recon(cx.dev, &b->params, b->buf->compact, compact_slot_bytes(b->params), b->buf->packed, b->total,
-                            b->buf->yuv, want_rgb_ ? b->buf->rgb : nullptr, &ms, &layout, &waves, err);
-        else if (!api_.recon_geometry) { rc = MVHP_FAILURE; err = "this device table has no output-geometry operation"; }
-        else
-            rc = api_.recon_geometry(cx.dev, &b->params, &b->geom, b->buf->compact, compact_slot_bytes(b->params), b->buf->packed,
-                                     b->total, b->buf->yuv, want_yuv_ ? b->buf->out_yuv : nullptr,
-                                     want_rgb_ ? b->buf->out_rgb : nullptr, &ms, &layout, &waves, err);
-        if (rc == MVHP_SUCCESS && score_ && !inject) {   // the scores, from the coded planes the operation above left in the batch buffer
-            float ms_s = 0.f;
-            rc = api_.luma_stats(cx.dev, &b->params, &b->geom, b->buf->yuv, b->total, (mvhp_luma_stats_t *)b->buf->stats, &ms_s, err);
-            ms += ms_s;
+        if (inject) err = "injected failure (test hook)";
+        else if (w_.score && !(api_.caps & CAP_SCORE)) err = "this device table has no picture-score operation";
+        else if (w_.jpeg && !(api_.caps & CAP_JPEG)) err = "this device table has no JPEG operation";
+        else if (b->use_geom && !w_.jpeg && !(api_.caps & CAP_GEOMETRY)) err = "this device table has no output-geometry operation";
+        else {
+            auto buf = [&](BufKind k) { return need(*b, k) ? b->buf->m[k].p : nullptr; };   // (a buffer may hold an earlier batch's kind)
+            BatchJob job{};
+            job.params = &b->params;
+            job.d_compact = buf(kCompact);
+            job.stride = need(*b, kCompact);
+            job.d_packed = buf(kPacked);
+            job.n = b->total;
+            job.d_yuv = buf(kYuv);
+            job.d_rgb = buf(kRgb);
+            job.geom = b->use_geom || w_.jpeg ? &b->geom : nullptr;
+            job.out_yuv = buf(kOutYuv);
+            job.out_rgb = buf(kOutRgb);
+            job.jpeg = w_.jpeg ? &jpeg_ : nullptr;
+            job.blob = buf(kJpegBlob);
+            job.blob_cap = (size_t)b->total * need(*b, kJpegBlob);
+            job.table = (mvhp_jpeg_entry_t *)buf(kJpegTab);
+            job.stats = (mvhp_luma_stats_t *)buf(kStats);
+            rc = api_.run_batch(cx.dev, job, done, err);
         }
+        const float ms = done.ms;
+        const int layout = done.layout;
         if (!cx.launched_once) {   // host time of the first call beyond the device time: code-object load, first-launch setup
             cx.launched_once = true;
             std::lock_guard<std::mutex> la(alloc_mu_);
@@ -1022,10 +1026,10 @@ void Engine::downloader(int k)
             b = batches_[cx.to_download.front()].get();
             cx.to_download.pop_front();
         }
-        // a batch with a geometry: only its output pictures come back
-        const size_t yb = b->use_geom ? mvhp_geometry_yuv_bytes(&b->geom) : mvhp_yuv_frame_bytes(&b->params);
-        const size_t rb = !want_rgb_ ? 0 : b->use_geom ? mvhp_geometry_rgb_bytes(&b->geom) : mvhp_rgb_frame_bytes(&b->params);
-        const uint8_t *d_y = b->use_geom ? b->buf->out_yuv : b->buf->yuv, *d_r = b->use_geom ? b->buf->out_rgb : b->buf->rgb;
+        // what comes back, from where, how many bytes per picture (a batch with a geometry: only its output pictures)
+        const BufKind ky = planes_kind(b->use_geom), kr = rgb_kind(b->use_geom);
+        const size_t yb = w_.yuv ? need(*b, ky) : 0, rb = w_.rgb ? need(*b, kr) : 0, sb = need(*b, kStats);
+        const uint8_t *d_y = b->buf->m[ky].p, *d_r = b->buf->m[kr].p, *d_s = b->buf->m[kStats].p;
         const int C = std::min(chunk_pictures(b->params), b->capacity);
         std::string fail;
         for (int g = 0; g < b->total && fail.empty(); g += C) {
@@ -1051,28 +1055,28 @@ void Engine::downloader(int k)
             float ms = 0.f, ms2 = 0.f;
             // MVHP_OUTPUT_SCORE: the chunk's records travel with it, one more piece of the chunk's own download call
             const mvhp_luma_stats_t *recs = nullptr;
-            const size_t score_bytes = score_ ? (size_t)n * sizeof(mvhp_luma_stats_t) : 0;
-            if (score_ && !grow(oc->stats, (size_t)C * sizeof(mvhp_luma_stats_t))) {
+            const size_t score_bytes = (size_t)n * sb;
+            if (!grow(oc->stats, (size_t)C * sb)) {
                 std::lock_guard<std::mutex> l(mu_);
                 put_out(oc);
                 fail = "out of page-locked host memory";
                 continue;
             }
-            if (score_) recs = (const mvhp_luma_stats_t *)oc->stats.p;
-            if (want_jpeg_) {   // the table rows of the chunk's pictures, then exactly the bytes they name, one piece per file
+            if (sb) recs = (const mvhp_luma_stats_t *)oc->stats.p;
+            if (w_.jpeg) {   // the table rows of the chunk's pictures, then exactly the bytes they name, one piece per file
                 const mvhp_jpeg_entry_t *tab = nullptr;
-                size_t base = 0, span = 0, moved = (size_t)n * sizeof(mvhp_jpeg_entry_t);
-                bool ok = grow(oc->tab, (size_t)C * sizeof(mvhp_jpeg_entry_t));
+                const size_t tb = need(*b, kJpegTab);
+                size_t base = 0, span = 0, moved = (size_t)n * tb;
+                bool ok = grow(oc->tab, (size_t)C * tb);
                 if (!ok) err = "out of page-locked host memory";
                 if (ok) {
                     void *dst[2] = {oc->tab.p, oc->stats.p};
-                    const void *src[2] = {b->buf->jpeg_tab + (size_t)g * sizeof(mvhp_jpeg_entry_t),
-                                          score_ ? b->buf->stats + (size_t)g * sizeof(mvhp_luma_stats_t) : nullptr};
+                    const void *src[2] = {b->buf->m[kJpegTab].p + (size_t)g * tb, sb ? d_s + (size_t)g * sb : nullptr};
                     size_t nb[2] = {moved, score_bytes};
-                    ok = api_.d2h(cx.dev, score_ ? 2 : 1, dst, src, nb, &ms, err) == MVHP_SUCCESS;
+                    ok = api_.d2h(cx.dev, sb ? 2 : 1, dst, src, nb, &ms, err) == MVHP_SUCCESS;
                     tab = (const mvhp_jpeg_entry_t *)oc->tab.p;
                 }
-                const size_t blob_cap = (size_t)b->total * mvhp_geometry_yuv_bytes(&b->geom);
+                const size_t blob_cap = (size_t)b->total * need(*b, kJpegBlob);
                 if (ok) {
                     base = (size_t)tab[0].offset;
                     for (int i = 0; i < n && ok; i++) {
@@ -1092,7 +1096,7 @@ void Engine::downloader(int k)
                     for (int i = 0; i < n; i++) {
                         if (tab[i].status != MVHP_JPEG_OK) continue;
                         dst.push_back(oc->rgb.p + (tab[i].offset - base));
-                        src.push_back(b->buf->jpeg_blob + tab[i].offset);
+                        src.push_back(b->buf->m[kJpegBlob].p + tab[i].offset);
                         nb.push_back(tab[i].length);
                         moved += tab[i].length;
                     }
@@ -1130,31 +1134,31 @@ void Engine::downloader(int k)
                 cv_.notify_all();
                 continue;
             }
-            bool ok = (!want_yuv_ || grow(oc->yuv, (size_t)C * yb)) && (!want_rgb_ || grow(oc->rgb, (size_t)C * rb));
+            bool ok = grow(oc->yuv, (size_t)C * yb) && grow(oc->rgb, (size_t)C * rb);
             if (!ok) err = "out of page-locked host memory";
             if (ok) {
                 void *dst[3];
                 const void *src[3];
                 size_t nb[3];
                 int np = 0;
-                if (want_yuv_) { dst[np] = oc->yuv.p; src[np] = d_y + (size_t)g * yb; nb[np++] = (size_t)n * yb; }
-                if (want_rgb_) { dst[np] = oc->rgb.p; src[np] = d_r + (size_t)g * rb; nb[np++] = (size_t)n * rb; }
-                if (score_) { dst[np] = oc->stats.p; src[np] = b->buf->stats + (size_t)g * sizeof(mvhp_luma_stats_t); nb[np++] = score_bytes; }
+                if (yb) { dst[np] = oc->yuv.p; src[np] = d_y + (size_t)g * yb; nb[np++] = (size_t)n * yb; }
+                if (rb) { dst[np] = oc->rgb.p; src[np] = d_r + (size_t)g * rb; nb[np++] = (size_t)n * rb; }
+                if (sb) { dst[np] = oc->stats.p; src[np] = d_s + (size_t)g * sb; nb[np++] = score_bytes; }
                 ok = api_.d2h(cx.dev, np, dst, src, nb, &ms, err) == MVHP_SUCCESS;
             }
             {
                 std::lock_guard<std::mutex> l(mu_);
                 if (ok) {
                     st_.d2h_s += (ms + ms2) * 1e-3;
-                    st_.d2h_bytes += (uint64_t)n * ((want_yuv_ ? yb : 0) + rb) + score_bytes;
+                    st_.d2h_bytes += (uint64_t)n * (yb + rb) + score_bytes;
                     oc->refs = 0;
                     for (int i = 0; i < n; i++) {
                         PicResult &r = results_[(size_t)b->seqs[(size_t)(g + i)]];
                         if (!r.parsed_ok || r.ready) continue;
                         r.rc = MVHP_SUCCESS;
                         r.oc = oc;
-                        r.yuv = want_yuv_ ? oc->yuv.p + (size_t)i * yb : nullptr;
-                        r.rgb = want_rgb_ ? oc->rgb.p + (size_t)i * rb : nullptr;
+                        r.yuv = yb ? oc->yuv.p + (size_t)i * yb : nullptr;
+                        r.rgb = rb ? oc->rgb.p + (size_t)i * rb : nullptr;
                         if (recs) r.geom.reserved[1] = mvblank::luma_score(recs[i].sum, recs[i].sumsq, recs[i].samples);
                         r.ready = true;
                         oc->refs++;
@@ -1203,17 +1207,17 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
     {
         std::lock_guard<std::mutex> l(mu_);
         s_ = &s; order_ = order; n_order_ = n_order; wanted_ = std::min(wanted, n_order);
-        want_jpeg_ = (out_mask & MVHP_OUT_JPEG) != 0;
-        want_rgb_ = !want_jpeg_ && (out_mask & 1) != 0;
-        want_yuv_ = !want_jpeg_ && (!want_rgb_ || (out_mask & 2) == 0);
+        w_.jpeg = (out_mask & MVHP_OUT_JPEG) != 0;
+        w_.rgb = !w_.jpeg && (out_mask & 1) != 0;
+        w_.yuv = !w_.jpeg && (!w_.rgb || (out_mask & 2) == 0);
         jpeg_ = mvhp_jpeg_params_t{};
-        if (want_jpeg_) {   // mvhp_output_request_t::reserved carries the encoder's parameters
+        if (w_.jpeg) {   // mvhp_output_request_t::reserved carries the encoder's parameters
             const uint32_t rsv = req ? req->reserved : 0;
             jpeg_.quality = (rsv & 0xffu) ? (int32_t)(rsv & 0xffu) : 75;
             jpeg_.restart_mcus = (rsv >> 8) & 0xffffu;
         }
         req_ = req ? *req : mvhp_output_request_t{};
-        score_ = (req_.flags & MVHP_OUTPUT_SCORE) != 0;
+        w_.score = (req_.flags & MVHP_OUTPUT_SCORE) != 0;
         req_.flags &= ~MVHP_OUTPUT_SCORE;   // (what is left decides the geometry: none = the path of a call without a request)
         stop_ = false; sink_waiting_ = false;
         pos_ = issued_ = consumed_ = ok_ = failed_ = 0;
@@ -1247,11 +1251,7 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         in_limit_ = (size_t)std::max(3, (host_threads_ + C - 1) / C + 1 + n_ctx);
         if (const int e = env_int("MINIVIDEO_IN_CHUNKS", 0)) in_limit_ = (size_t)std::max(2, std::min(64, e));   // developer aid
         {   // the largest batch this call can form on a context: what a placed arena is sized for
-            int cap = opts_.batch_pictures > 0 ? opts_.batch_pictures : ((n_order_ >= 4096 * n_ctx) ? 2048 : 1024);
-            const size_t per_pic = compact_slot_bytes(p0) + mvhp_packed_frame_bytes(&p0) + mvhp_yuv_frame_bytes(&p0) + mvhp_rgb_frame_bytes(&p0);
-            size_t budget = ctx_[0].mem_budget;
-            for (const Ctx &c : ctx_) budget = std::min(budget, c.mem_budget);
-            cap = std::min<int>(cap, (int)std::min<size_t>(1 << 20, std::max<size_t>(1, budget / std::max<size_t>(1, per_pic))));
+            int cap = launch_cap(batch_picture_bytes(p0, coded_geometry(p0), false, kPlanesAndRgb));
             cap = std::max(1, std::min(cap, (wanted_ + n_ctx - 1) / n_ctx));
             job_cap_ = 1;   // the largest batch the ramp / cap / taper will actually form when nothing fails
             for (int rem = wanted_, id = 0; rem > 0; id++) {

@@ -4,7 +4,8 @@
 // Replaces, as one pipeline, the reference's serial loop: NAL loop h264.c:76-188 -> decode_slice h264_slice.c:64-109
 // -> macroblock loop h264_slice.c:1046-1139 -> export_idr export.c:618-767.
 //
-// The engine is plain C++ over a small table of device operations (DeviceApi), so that the threading can be built and
+// The engine is plain C++ over a small table of device operations (DeviceApi: allocation, the two copies, and one operation
+// that runs a whole batch from a descriptor, BatchJob), so that the threading can be built and
 // checked on a CPU-only box against a stub device (tools/engine_harness.cpp, tests/test_engine_harness.py: ThreadSanitizer + AddressSanitizer); the product's table is HIP
 // (csrc/hip/hotpath_abi.hip) and there is no CPU implementation of it in the library.
 #pragma once
@@ -21,6 +22,32 @@ namespace mvengine {
 
 struct DevCtx;   // one device context: a reconstruction context plus its upload / compute / download queues
 
+// Everything one batch runs on the device, in order, on the context's compute queue: compact pictures (`stride` bytes apart) ->
+// packed records in d_packed (scratch) -> planes -> the passes the fields below ask for.
+struct BatchJob {
+    const mvhp_stream_params_t *params;
+    const void *d_compact; size_t stride; void *d_packed; int n;
+    uint8_t *d_yuv;   // n x planes of the coded size: always written (after the deblocking filter where params ask for it).  The
+                      // output of a job with nothing below, the scratch every later pass reads otherwise
+    uint8_t *d_rgb;   // fused RGB of the coded size, or NULL.  Only without a resample pass and without JPEG: those reconstruct
+                      // planes only, without the fused colour epilogue
+    const mvhp_output_geometry_t *geom;   // of the n pictures; NULL: the coded size, nothing below but `stats` may be set
+    uint8_t *out_yuv, *out_rgb;   // mvhp_resample_dev of d_yuv into n pictures of `geom`: planes and / or RGB (either may be NULL);
+                                  // both NULL: no resample pass (only with `jpeg`: files of the coded size, geom names that size)
+    const mvhp_jpeg_params_t *jpeg;   // NULL: no encoder.  Else mvhp_jpeg_encode_dev of the n pictures of `geom` -- out_yuv where a
+                                      // resample pass ran, else d_yuv -- into `blob` (blob_cap bytes) and `table` (n entries)
+    uint8_t *blob; size_t blob_cap; mvhp_jpeg_entry_t *table;
+    mvhp_luma_stats_t *stats;   // NULL: no picture scores.  Else mvhp_luma_stats_dev over the crop rectangle of `geom` (the whole
+                                // picture without one) on the n coded planes in d_yuv -> n records
+};
+struct BatchDone {
+    float ms;            // device-side duration of the whole job, one bracketed interval
+    int layout, waves;   // of the reconstruction launch
+};
+
+// what run_batch can do beyond pictures of the coded size; a job that needs a missing bit fails in the engine, with a message
+enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4 };
+
 // Every operation blocks its calling thread until the device has finished it; the engine runs one thread per queue
 // and context, which is what overlaps upload(k+1), kernel(k) and download(k-1).  *ms = device-side duration.
 struct DeviceApi {
@@ -36,33 +63,12 @@ struct DeviceApi {
     int    (*h2d)(DevCtx *c, int n, void *const *d_dst, const void *const *h_src, const size_t *bytes, float *ms, std::string &err);
     // n pieces in one go (the planes and the RGB of an output chunk: one wait instead of two)
     int    (*d2h)(DevCtx *c, int n, void *const *h_dst, const void *const *d_src, const size_t *bytes, float *ms, std::string &err);
-    // compact pictures (`stride` bytes apart) -> packed records in d_packed (scratch) -> planes (+ RGB)
-    int    (*recon)(DevCtx *c, const mvhp_stream_params_t *p, const void *d_compact, size_t stride, void *d_packed,
-                    int n_pictures, uint8_t *d_yuv, uint8_t *d_rgb, float *ms, int *layout, int *waves, std::string &err);
+    int    (*run_batch)(DevCtx *c, const BatchJob &job, BatchDone &done, std::string &err);
+    uint32_t caps;   // CAP_*
     // optional (may be NULL): `sets` x 4 batch buffers {compact, records, planes, RGB} inside one arena, records / planes / RGB
     // each in a group of the device's memory regions of its own (mvhp_placed_alloc_sets); ptrs[s * 4 + i]; nullptr = failed
     void  *(*placed_alloc)(DevCtx *c, int sets, const size_t bytes[4], void **ptrs);
     void   (*placed_free)(DevCtx *c, void *arena);
-    // optional (may be NULL: a batch with an output geometry then fails), last so that a positional initialiser of the
-    // operations above still compiles: `recon` without its fused colour epilogue into d_yuv_coded (scratch: planes of the coded
-    // size), the deblocking filter when p asks for it, then mvhp_resample_dev into n pictures of geometry g -- planes into
-    // d_yuv_out and / or RGB into d_rgb_out (either may be NULL)
-    int    (*recon_geometry)(DevCtx *c, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const void *d_compact,
-                             size_t stride, void *d_packed, int n_pictures, uint8_t *d_yuv_coded, uint8_t *d_yuv_out,
-                             uint8_t *d_rgb_out, float *ms, int *layout, int *waves, std::string &err);
-    // optional (may be NULL: a call with MVHP_OUT_JPEG then fails), last for the same reason: `recon` planes only into d_yuv_coded,
-    // the deblocking filter when p asks for it, mvhp_resample_dev into d_yuv_out when `resample` (g then differs from the coded
-    // size; otherwise d_yuv_out is NULL), then mvhp_jpeg_encode_dev of the n pictures of geometry g into d_blob (cap_bytes) and
-    // d_table (n entries)
-    int    (*recon_jpeg)(DevCtx *c, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, int resample,
-                         const mvhp_jpeg_params_t *jp, const void *d_compact, size_t stride, void *d_packed, int n_pictures,
-                         uint8_t *d_yuv_coded, uint8_t *d_yuv_out, uint8_t *d_blob, size_t cap_bytes, mvhp_jpeg_entry_t *d_table,
-                         float *ms, int *layout, int *waves, std::string &err);
-    // optional (may be NULL: a call with MVHP_OUTPUT_SCORE then fails), last for the same reason: mvhp_luma_stats_dev over the crop
-    // rectangle of g on the n coded planes that recon / recon_geometry / recon_jpeg left in d_yuv_coded (after the deblocking
-    // filter, where p asks for it) -> n records in d_stats; *ms = its device-side duration
-    int    (*luma_stats)(DevCtx *c, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const uint8_t *d_yuv_coded,
-                         int n_pictures, mvhp_luma_stats_t *d_stats, float *ms, std::string &err);
 };
 
 class Engine;

@@ -6,8 +6,8 @@
 //
 // usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes> [jpeg | score]]]
 // The fourth argument adds the geometry mode: mvhp_engine_decode_ex and minivideo_decode under MINIVIDEO_CROP /
-// MINIVIDEO_THUMBNAIL against the stub's output-geometry operation.  A fifth argument adds the JPEG mode (MVHP_OUT_JPEG) or the
-// score mode (MVHP_OUTPUT_SCORE against the stub's picture-score operation, which sums the stub's coded planes on the CPU).
+// MINIVIDEO_THUMBNAIL against the stub's resample targets.  A fifth argument adds the JPEG mode (MVHP_OUT_JPEG) or the
+// score mode (MVHP_OUTPUT_SCORE against the stub's picture scores, which sum the stub's coded planes on the CPU).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -100,32 +100,9 @@ void expand_compact(const uint8_t *pic, size_t mbs, uint8_t *packed)
         }
     }
 }
-int stub_recon(DevCtx *, const mvhp_stream_params_t *p, const void *d_compact, size_t stride, void *d_packed, int n, uint8_t *d_yuv,
-               uint8_t *d_rgb, float *ms, int *layout, int *waves, std::string &)
-{
-    g_recon_calls++;
-    const size_t pb = mvhp_packed_frame_bytes(p), yb = mvhp_yuv_frame_bytes(p), rb = mvhp_rgb_frame_bytes(p);
-    for (int i = 0; i < n; i++)
-        expand_compact((const uint8_t *)d_compact + (size_t)i * stride, (size_t)p->width_mbs * p->height_mbs, (uint8_t *)d_packed + (size_t)i * pb);
-    for (int i = 0; i < n; i++) {
-        const uint64_t h = checksum((const uint8_t *)d_packed + (size_t)i * pb, pb);
-        memset(d_yuv + (size_t)i * yb, 0x5a, yb);
-        memcpy(d_yuv + (size_t)i * yb, &h, sizeof(h));
-        if (d_rgb) {
-            memset(d_rgb + (size_t)i * rb, 0xa5, rb);
-            memcpy(d_rgb + (size_t)i * rb + 8, &h, sizeof(h));
-        }
-    }
-    std::this_thread::sleep_for(std::chrono::microseconds(200));
-    if (ms) *ms = 0.2f;
-    if (layout) *layout = MVHP_LAYOUT_ROWS;
-    if (waves) *waves = 8;
-    return MVHP_SUCCESS;
-}
-
-// The coded planes the geometry and JPEG operations leave behind: 0x11, the luma plane filled with the eight bytes of the records'
-// checksum over and over, so that every rectangle of it sums to something that depends on the picture (score mode).  The plain
-// operation's planes are its output: 0x5a with the checksum in bytes 0-7.
+// The coded planes a job with a geometry or JPEG leaves behind: 0x11, the luma plane filled with the eight bytes of the records'
+// checksum over and over, so that every rectangle of it sums to something that depends on the picture (score mode).  The planes of
+// a job of the coded size are its output: 0x5a with the checksum in bytes 0-7.
 uint8_t coded_luma(uint64_t h, bool pattern, size_t j) { return pattern ? (uint8_t)(h >> (8 * (j & 7))) : j < 8 ? (uint8_t)(h >> (8 * j)) : 0x5a; }
 void fill_coded(uint8_t *pic, size_t yb, uint64_t h)
 {
@@ -146,114 +123,107 @@ mvhp_luma_stats_t expected_stats(uint64_t h, bool pattern, const mvhp_stream_par
     return st;
 }
 
-// The picture-score operation: honest sums over the rectangle of the coded planes the batch buffer holds.
-std::atomic<int> g_stats_calls{0};
-int stub_luma_stats(DevCtx *, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const uint8_t *d_yuv_coded, int n,
-                    mvhp_luma_stats_t *d_stats, float *ms, std::string &err)
-{
-    g_stats_calls++;
-    if (!p || !g || !d_yuv_coded || !d_stats || n <= 0 || g->crop_w == 0 || g->crop_h == 0 || g->crop_x + g->crop_w > p->width_mbs * 16 ||
-        g->crop_y + g->crop_h > p->height_mbs * 16) { err = "stub: picture-score launch without buffers or rectangle"; return MVHP_FAILURE; }
-    const size_t yb = mvhp_yuv_frame_bytes(p), Wp = (size_t)p->width_mbs * 16;
-    for (int i = 0; i < n; i++) {
-        mvhp_luma_stats_t st{};
-        const uint8_t *pic = d_yuv_coded + (size_t)i * yb;
-        for (uint32_t y = g->crop_y; y < g->crop_y + g->crop_h; y++)
-            for (uint32_t x = g->crop_x; x < g->crop_x + g->crop_w; x++) {
-                const uint64_t v = pic[(size_t)y * Wp + x];
-                st.sum += v;
-                st.sumsq += v * v;
-            }
-        st.samples = g->crop_w * g->crop_h;
-        d_stats[i] = st;
-    }
-    if (ms) *ms = 0.05f;
-    return MVHP_SUCCESS;
-}
-
-// The output-geometry operation: the coded planes are written in full (the scratch buffer must hold them), every output
-// picture is filled up to its last byte (the output buffers must hold n pictures of the geometry) and stamped: planes
-// 0x5a, checksum of the records in bytes 0-7, 0x77 in the last byte; RGB 0xa5, the checksum in bytes 8-15, 0x78 last.
-constexpr uint8_t kLastYuv = 0x77, kLastRgb = 0x78;
-int stub_recon_geometry(DevCtx *, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, const void *d_compact, size_t stride,
-                        void *d_packed, int n, uint8_t *d_yuv_coded, uint8_t *d_yuv_out, uint8_t *d_rgb_out, float *ms, int *layout,
-                        int *waves, std::string &err)
-{
-    g_geometry_calls++;
-    if (!g || !d_yuv_coded || (!d_yuv_out && !d_rgb_out)) { err = "stub: geometry launch without buffers"; return MVHP_FAILURE; }
-    const size_t pb = mvhp_packed_frame_bytes(p), yb = mvhp_yuv_frame_bytes(p);
-    const size_t gy = mvhp_geometry_yuv_bytes(g), gr = mvhp_geometry_rgb_bytes(g);
-    for (int i = 0; i < n; i++)
-        expand_compact((const uint8_t *)d_compact + (size_t)i * stride, (size_t)p->width_mbs * p->height_mbs, (uint8_t *)d_packed + (size_t)i * pb);
-    for (int i = 0; i < n; i++) {
-        const uint64_t h = checksum((const uint8_t *)d_packed + (size_t)i * pb, pb);
-        fill_coded(d_yuv_coded + (size_t)i * yb, yb, h);
-        if (d_yuv_out) {
-            memset(d_yuv_out + (size_t)i * gy, 0x5a, gy);
-            memcpy(d_yuv_out + (size_t)i * gy, &h, sizeof(h));
-            d_yuv_out[(size_t)i * gy + gy - 1] = kLastYuv;
-        }
-        if (d_rgb_out) {
-            memset(d_rgb_out + (size_t)i * gr, 0xa5, gr);
-            memcpy(d_rgb_out + (size_t)i * gr + 8, &h, sizeof(h));
-            d_rgb_out[(size_t)i * gr + gr - 1] = kLastRgb;
-        }
-    }
-    std::this_thread::sleep_for(std::chrono::microseconds(200));
-    if (ms) *ms = 0.2f;
-    if (layout) *layout = MVHP_LAYOUT_ROWS;
-    if (waves) *waves = 8;
-    return MVHP_SUCCESS;
-}
-
-// The JPEG operation: the coded planes (and the output planes of a batch with a geometry) are written in full, and every picture
-// gets a "file" whose length depends on its records -- 32 + checksum % (half the raw picture) bytes of 0x3c, the checksum in bytes
-// 0-7, 0x79 last -- at the next multiple of 16 of the blob; a picture whose checksum is a multiple of 5 is reported too big.
-constexpr uint8_t kLastJpeg = 0x79;
-std::atomic<int> g_jpeg_calls{0};
+// The one batch operation.  Every job expands its pictures and leaves coded planes; then, as the descriptor asks:
+// * nothing more (pictures of the coded size): the planes are the output, 0x5a with the checksum of the records in bytes 0-7; RGB
+//   0xa5 with the checksum in bytes 8-15;
+// * resample targets: the coded planes are written in full (the scratch buffer must hold them), every output picture is filled up
+//   to its last byte (the output buffers must hold n pictures of the geometry) and stamped: planes 0x5a, checksum of the records in
+//   bytes 0-7, 0x77 in the last byte; RGB 0xa5, the checksum in bytes 8-15, 0x78 last;
+// * JPEG: the coded planes (and the output planes of a batch with a resample pass) are written in full, and every picture gets a
+//   "file" whose length depends on its records -- 32 + checksum % (half the raw picture) bytes of 0x3c, the checksum in bytes 0-7,
+//   0x79 last -- at the next multiple of 16 of the blob; a picture whose checksum is a multiple of 5 is reported too big;
+// * scores: honest sums over the rectangle of the coded planes the batch buffer holds.
+constexpr uint8_t kLastYuv = 0x77, kLastRgb = 0x78, kLastJpeg = 0x79;
+std::atomic<int> g_jpeg_calls{0}, g_stats_calls{0};
 size_t stub_jpeg_length(uint64_t h, size_t raw) { return 32 + (size_t)(h % (raw / 2)); }
 bool stub_jpeg_too_big(uint64_t h) { return h % 5 == 0; }
-int stub_recon_jpeg(DevCtx *, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, int resample, const mvhp_jpeg_params_t *jp,
-                    const void *d_compact, size_t stride, void *d_packed, int n, uint8_t *d_yuv_coded, uint8_t *d_yuv_out,
-                    uint8_t *d_blob, size_t cap, mvhp_jpeg_entry_t *d_table, float *ms, int *layout, int *waves, std::string &err)
+int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &done, std::string &err)
 {
-    g_jpeg_calls++;
-    if (!g || !jp || !d_yuv_coded || !d_blob || !d_table || (resample != 0) != (d_yuv_out != nullptr) || jp->quality < 1 || jp->quality > 100) {
+    const mvhp_stream_params_t *p = j.params;
+    const mvhp_output_geometry_t *g = j.geom;
+    const bool resample = j.out_yuv || j.out_rgb;
+    (j.jpeg ? g_jpeg_calls : resample ? g_geometry_calls : g_recon_calls)++;
+    if (!j.d_yuv || (!j.jpeg && (g != nullptr) != resample)) { err = "stub: geometry launch without buffers"; return MVHP_FAILURE; }
+    // (JPEG: a resample pass exactly where the pictures are not of the coded size)
+    if (j.jpeg && (!g || !j.blob || !j.table || j.out_rgb || j.jpeg->quality < 1 || j.jpeg->quality > 100 ||
+                   (j.out_yuv != nullptr) != (g->out_w != p->width_mbs * 16 || g->out_h != p->height_mbs * 16))) {
         err = "stub: JPEG launch without buffers or parameters";
         return MVHP_FAILURE;
     }
-    const size_t pb = mvhp_packed_frame_bytes(p), yb = mvhp_yuv_frame_bytes(p), gy = mvhp_geometry_yuv_bytes(g);
-    if (cap != (size_t)n * gy) { err = "stub: the blob is not n raw pictures long"; return MVHP_FAILURE; }
+    const int n = j.n;
+    const size_t pb = mvhp_packed_frame_bytes(p), yb = mvhp_yuv_frame_bytes(p), rb = mvhp_rgb_frame_bytes(p);
+    const size_t gy = mvhp_geometry_yuv_bytes(g), gr = mvhp_geometry_rgb_bytes(g);
+    if (j.jpeg && j.blob_cap != (size_t)n * gy) { err = "stub: the blob is not n raw pictures long"; return MVHP_FAILURE; }
+    mvhp_output_geometry_t rect{};   // of the scores: the crop of the geometry, the coded picture without one
+    rect.crop_w = p->width_mbs * 16;
+    rect.crop_h = p->height_mbs * 16;
+    if (g) rect = *g;
+    if (j.stats && (n <= 0 || rect.crop_w == 0 || rect.crop_h == 0 || rect.crop_x + rect.crop_w > p->width_mbs * 16 ||
+                    rect.crop_y + rect.crop_h > p->height_mbs * 16)) { err = "stub: picture-score launch without buffers or rectangle"; return MVHP_FAILURE; }
     for (int i = 0; i < n; i++)
-        expand_compact((const uint8_t *)d_compact + (size_t)i * stride, (size_t)p->width_mbs * p->height_mbs, (uint8_t *)d_packed + (size_t)i * pb);
-    if (d_yuv_out) memset(d_yuv_out, 0x12, (size_t)n * gy);
+        expand_compact((const uint8_t *)j.d_compact + (size_t)i * j.stride, (size_t)p->width_mbs * p->height_mbs, (uint8_t *)j.d_packed + (size_t)i * pb);
+    if (j.jpeg && j.out_yuv) memset(j.out_yuv, 0x12, (size_t)n * gy);
     size_t pos = 0;
     for (int i = 0; i < n; i++) {
-        const uint64_t h = checksum((const uint8_t *)d_packed + (size_t)i * pb, pb);
-        fill_coded(d_yuv_coded + (size_t)i * yb, yb, h);
-        const size_t len = stub_jpeg_length(h, gy);
-        mvhp_jpeg_entry_t e{pos, 0, MVHP_JPEG_TOO_BIG};
-        if (!stub_jpeg_too_big(h) && pos + len <= cap) {
-            memset(d_blob + pos, 0x3c, len);
-            memcpy(d_blob + pos, &h, sizeof(h));
-            d_blob[pos + len - 1] = kLastJpeg;
-            e.length = (uint32_t)len;
-            e.status = MVHP_JPEG_OK;
-            pos = (pos + len + 15) & ~(size_t)15;
+        const uint64_t h = checksum((const uint8_t *)j.d_packed + (size_t)i * pb, pb);
+        uint8_t *coded = j.d_yuv + (size_t)i * yb;
+        if (g) fill_coded(coded, yb, h);
+        else {
+            memset(coded, 0x5a, yb);
+            memcpy(coded, &h, sizeof(h));
         }
-        d_table[i] = e;
+        if (j.d_rgb && !g) {
+            memset(j.d_rgb + (size_t)i * rb, 0xa5, rb);
+            memcpy(j.d_rgb + (size_t)i * rb + 8, &h, sizeof(h));
+        }
+        if (j.out_yuv && !j.jpeg) {
+            memset(j.out_yuv + (size_t)i * gy, 0x5a, gy);
+            memcpy(j.out_yuv + (size_t)i * gy, &h, sizeof(h));
+            j.out_yuv[(size_t)i * gy + gy - 1] = kLastYuv;
+        }
+        if (j.out_rgb) {
+            memset(j.out_rgb + (size_t)i * gr, 0xa5, gr);
+            memcpy(j.out_rgb + (size_t)i * gr + 8, &h, sizeof(h));
+            j.out_rgb[(size_t)i * gr + gr - 1] = kLastRgb;
+        }
+        if (j.jpeg) {
+            const size_t len = stub_jpeg_length(h, gy);
+            mvhp_jpeg_entry_t e{pos, 0, MVHP_JPEG_TOO_BIG};
+            if (!stub_jpeg_too_big(h) && pos + len <= j.blob_cap) {
+                memset(j.blob + pos, 0x3c, len);
+                memcpy(j.blob + pos, &h, sizeof(h));
+                j.blob[pos + len - 1] = kLastJpeg;
+                e.length = (uint32_t)len;
+                e.status = MVHP_JPEG_OK;
+                pos = (pos + len + 15) & ~(size_t)15;
+            }
+            j.table[i] = e;
+        }
+        if (j.stats) {
+            mvhp_luma_stats_t st{};
+            const size_t Wp = (size_t)p->width_mbs * 16;
+            for (uint32_t y = rect.crop_y; y < rect.crop_y + rect.crop_h; y++)
+                for (uint32_t x = rect.crop_x; x < rect.crop_x + rect.crop_w; x++) {
+                    const uint64_t v = coded[(size_t)y * Wp + x];
+                    st.sum += v;
+                    st.sumsq += v * v;
+                }
+            st.samples = rect.crop_w * rect.crop_h;
+            j.stats[i] = st;
+        }
     }
     std::this_thread::sleep_for(std::chrono::microseconds(200));
-    if (ms) *ms = 0.2f;
-    if (layout) *layout = MVHP_LAYOUT_ROWS;
-    if (waves) *waves = 8;
+    done.ms = j.stats ? 0.25f : 0.2f;
+    done.layout = MVHP_LAYOUT_ROWS;
+    done.waves = 8;
+    if (j.stats) g_stats_calls++;
     return MVHP_SUCCESS;
 }
 
 mvengine::DeviceApi g_stub = {stub_device_count, stub_host_alloc, stub_host_free, stub_ctx_create, stub_ctx_destroy,
-                                    stub_dev_alloc, stub_dev_free, stub_dev_free_bytes, stub_copy_n, stub_copy_n, stub_recon,
-                                    nullptr, nullptr,   // (no placed arena on the stub device)
-                                    stub_recon_geometry, stub_recon_jpeg, stub_luma_stats};
+                                    stub_dev_alloc, stub_dev_free, stub_dev_free_bytes, stub_copy_n, stub_copy_n, stub_run_batch,
+                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE,
+                                    nullptr, nullptr};   // (no placed arena on the stub device)
 
 uint64_t picture_checksum(const mvhp_stream &s, int idr)
 {
@@ -266,7 +236,7 @@ uint64_t picture_checksum(const mvhp_stream &s, int idr)
 }
 
 // sink of the geometry mode: the right picture, in order, with the geometry mvhp_output_geometry gives for it and buffers that
-// reach to the last byte of that geometry (pictures of the coded size come from stub_recon: no end mark)
+// reach to the last byte of that geometry (pictures of the coded size are the stub's coded planes: no end mark)
 struct CheckG {
     const mvhp_stream *s = nullptr;
     mvhp_output_request_t req{};
@@ -1013,7 +983,7 @@ int main(int argc, char **argv)
             // 9 coded-size runs without JPEG its planes are 0x5a past their first 8 bytes, and the scores of pictures nearly agree.
             EXPECT(distinct_checked >= 27);
             {   // a device table without the operation: every picture of the call fails with the message
-                g_stub.luma_stats = nullptr;
+                g_stub.caps &= ~mvengine::CAP_SCORE;
                 mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 4;
                 CheckS c; mvhp_decode_stats_t st;
                 const int calls0 = g_stats_calls, recon0 = g_recon_calls + g_geometry_calls + g_jpeg_calls;
@@ -1022,7 +992,7 @@ int main(int argc, char **argv)
                 EXPECT(g_recon_calls + g_geometry_calls + g_jpeg_calls == recon0);
                 CheckG cg;   // ... and a call without the flag is not affected
                 EXPECT(run_ex("score: table without it, off", o, s3, order, 0, crop, cg, st) == MVHP_SUCCESS && cg.bad == 0);
-                g_stub.luma_stats = stub_luma_stats;
+                g_stub.caps |= mvengine::CAP_SCORE;
             }
             {   // minivideo_decode under MINIVIDEO_SKIP_BLANK=1 on the stub device: two engine calls on one engine, the second one's
                 // files written over the first one's.  With the threshold at its maximum every stub picture is blank, so each slot
