@@ -22,6 +22,14 @@
  *     alike.  A malformed MINIVIDEO_THUMBNAIL ("abc", "0x10", "320", a side below 2) is not ignored: minivideo_decode()
  *     returns FAILURE with a message before any device work.  A picture whose crop leaves nothing is skipped like a picture
  *     that does not decode;
+ *   - opt-in, outside the reference's behaviour (which reads an MP4 track's display matrix, traces it and drops it,
+ *     demuxer/mp4/mp4.c:1167-1197) and independent of the switches above: MINIVIDEO_ROTATE=auto|0|90|180|270 turns the
+ *     pictures on the GPU before they are written.  "auto" applies the rotation of the MP4 video track's tkhd matrix when it
+ *     is a pure quarter-turn rotation (a phone's portrait clip comes out upright; mirrored, scaled or sheared matrices and
+ *     Annex-B input: no turn), an angle turns by that many degrees clockwise whatever the file says.  Every format is written
+ *     at the turned size (1080 x 1920 for a 90-degree 1920 x 1080 clip), a MINIVIDEO_THUMBNAIL box is the box of the turned
+ *     picture, file names do not change; 0, the empty string and a rotation that comes to 0 are the files without the switch.
+ *     Any other value ("45", "90x") is not ignored: minivideo_decode() returns FAILURE with a message before any device work;
  *   - PICTURE_JPG is written as PNG, as a reference built without libjpeg does (export.c:644-690).  Opt-in, outside the
  *     reference's behaviour and independent of the switches above: with MINIVIDEO_JPEG=1 PICTURE_JPG writes <name>[_k].jpg,
  *     baseline JFIF files coded on the GPU from the 4:2:0 planes as export.c:341-430 does with libjpeg (2x2 / 1x1 / 1x1

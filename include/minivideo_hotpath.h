@@ -195,6 +195,12 @@ MVHP_EXPORT int  mvhp_stream_open_ex(const uint8_t *data, size_t size, uint32_t 
 MVHP_EXPORT int  mvhp_stream_open_mp4(const uint8_t *data, size_t size, mvhp_stream_t **out);
 MVHP_EXPORT void mvhp_stream_close(mvhp_stream_t *s);
 MVHP_EXPORT int  mvhp_stream_idr_count(const mvhp_stream_t *s);
+/* The display rotation of the stream, clockwise, in degrees: 0, 90, 180 or 270.  MP4: the video track's tkhd matrix when it is
+ * one of the four pure rotations (a mirrored, scaled or sheared matrix, non-zero u / v, a w other than 1.0 or a box too short
+ * for the matrix give 0; the translation is ignored; the movie header's matrix is not read).  Annex-B streams: 0.  The
+ * reference reads the matrix, traces it and drops it (demuxer/mp4/mp4.c:1167-1197).  Information only: nothing turns unless an
+ * output request asks for it ("Orientation" below). */
+MVHP_EXPORT int  mvhp_stream_rotation(const mvhp_stream_t *s);
 /* Parameters in force for IDR picture `idr` (valid after mvhp_stream_open). */
 MVHP_EXPORT int  mvhp_stream_params(const mvhp_stream_t *s, int idr, mvhp_stream_params_t *out);
 /* Entropy-decode IDR picture `idr` into `packed` (mvhp_packed_frame_bytes()).
@@ -264,6 +270,14 @@ typedef struct mvhp_output_geometry {
 #define MVHP_OUTPUT_BOX  2u   /* ... fitted into box_w x box_h (implies MVHP_OUTPUT_CROP); box sides >= 2     */
 #define MVHP_OUTPUT_SCORE 4u  /* mvhp_engine_decode_ex: every picture's score in g->reserved[1] ("Picture scores" below); changes no
                                  picture: a request with this flag alone still means pictures of the coded size */
+/* Orientation (opt-in; DESIGN.md 3 "Orientation"): pictures turned by quarter turns, clockwise.  MVHP_OUTPUT_ORIENT applies the
+ * stream's own rotation (mvhp_stream_rotation), MVHP_OUTPUT_ROTATE(q) adds q further quarter turns; what is applied is the sum
+ * modulo 4 (mvhp_output_turns).  "auto" is the flag alone, an explicit angle the field alone.  Both compose with every flag
+ * above.  A sum of 0 is the request without these bits: the same paths, launches, buffers and bytes. */
+#define MVHP_OUTPUT_ORIENT 8u
+#define MVHP_OUTPUT_ROTATE_SHIFT 4
+#define MVHP_OUTPUT_ROTATE_MASK  0x30u
+#define MVHP_OUTPUT_ROTATE(q) (((uint32_t)(q) & 3u) << MVHP_OUTPUT_ROTATE_SHIFT)
 typedef struct mvhp_output_request {
     uint32_t flags;           /* MVHP_OUTPUT_*; 0 = the coded size (what the reference writes)                  */
     uint32_t box_w, box_h;
@@ -274,7 +288,12 @@ typedef struct mvhp_output_request {
  * the coded size).  Information only: it changes nothing.  MVHP_FAILURE (mvhp_stream_last_error() says why) when the
  * picture has no parameter sets or the crop leaves nothing (w <= 0 or h <= 0). */
 MVHP_EXPORT int    mvhp_stream_crop(const mvhp_stream_t *s, int idr, mvhp_output_geometry_t *out);
-/* The output geometry of picture `idr` under `req` (NULL or flags 0: the coded size, no crop). */
+/* The quarter turns (0..3, clockwise) that `req` applies to pictures of `s` (NULL request: 0). */
+MVHP_EXPORT int    mvhp_output_turns(const mvhp_stream_t *s, const mvhp_output_request_t *req);
+/* The output geometry of picture `idr` under `req` (NULL or flags 0: the coded size, no crop).  It is what the sink gets: under a
+ * request that turns by an odd number of quarter turns the geometry is formed with box_w and box_h exchanged and out_w / out_h
+ * are exchanged afterwards (1920 x 1080 in a 320 x 320 box: 320 x 180 unturned, 180 x 320 turned); crop_* stay in coded
+ * coordinates.  The bytes of a picture (mvhp_geometry_*_bytes) do not change with the turn. */
 MVHP_EXPORT int    mvhp_output_geometry(const mvhp_stream_t *s, int idr, const mvhp_output_request_t *req,
                                         mvhp_output_geometry_t *out);
 /* The size rule alone: cw x ch (even) fitted into bw x bh (each >= 2) -> *ow x *oh. */
@@ -288,6 +307,25 @@ MVHP_EXPORT size_t mvhp_geometry_rgb_bytes(const mvhp_output_geometry_t *g);
  * (NULL = the context's own). */
 MVHP_EXPORT int    mvhp_resample_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
                                      const uint8_t *d_yuv_coded, int n, uint8_t *d_yuv_out, uint8_t *d_rgb_out, void *stream);
+
+/* Orientation on the device (orient.hip): n pictures turned by `quarter_turns` (0..3, clockwise) into planes (d_yuv_out, may be
+ * NULL) and / or RGB (d_rgb_out, may be NULL), both dense and 4-byte aligned like the outputs of mvhp_resample_dev.  `g` is the
+ * geometry BEFORE the turn.  With MVHP_ORIENT_SRC_CODED in src_flags, d_src holds n coded pictures of `p` (16-byte aligned) and
+ * the crop rectangle of g is read out of them (out_w / out_h must equal crop_w / crop_h: a turned crop needs no copy pass
+ * first); without it d_src holds n dense pictures of g->out_w x g->out_h (4-byte aligned), as mvhp_resample_dev leaves them (p
+ * is not read and may be NULL).  Output pictures are out_h x out_w for odd turns and out_w x out_h for even ones.  For a source
+ * plane S of w x h and its output O (each plane with its own size):
+ *     1 turn:  O[y][x] = S[h-1-x][y]       2 turns: O[y][x] = S[h-1-y][w-1-x]       3 turns: O[y][x] = S[x][w-1-y]
+ * RGB is made from the TURNED planes with the reference's integer formula and 2x2-nearest chroma.  All sides are even, so a 2x2
+ * chroma cell of the source is a 2x2 cell of the output: RGB of the turned planes equals the turned RGB of the source.  Zero
+ * turns is valid: a crop or copy plus colour conversion.  n = 0 does nothing; turns outside 0..3, n < 0, odd or zero sizes and
+ * a rectangle outside the coded picture are refused (MVHP_FAILURE) before anything is launched.  Asynchronous on `stream` (NULL
+ * = the context's own).  Nothing is shared between workgroups, no kernel waits and nothing survives a launch: safe under stream
+ * capture, and two calls on two streams do not meet. */
+#define MVHP_ORIENT_SRC_CODED 1u
+MVHP_EXPORT int    mvhp_orient_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, int quarter_turns,
+                                   uint32_t src_flags, const uint8_t *d_src, int n, uint8_t *d_yuv_out, uint8_t *d_rgb_out,
+                                   void *stream);
 
 /* ---------------------------------------------------------------------------
  * JPEG output (opt-in; DESIGN.md 3 "JPEG output"): baseline sequential JFIF files made on the device from planar pictures, the

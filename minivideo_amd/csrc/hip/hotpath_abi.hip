@@ -442,6 +442,58 @@ MVHP_EXPORT int mvhp_resample_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p, 
     return MVHP_SUCCESS;
 }
 
+MVHP_EXPORT int mvhp_orient_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, int quarter_turns,
+                                uint32_t src_flags, const uint8_t *d_src, int n, uint8_t *d_yuv_out, uint8_t *d_rgb_out, void *stream)
+{
+    const bool coded = (src_flags & MVHP_ORIENT_SRC_CODED) != 0;
+    if (!c || !g || !d_src || n < 0 || quarter_turns < 0 || quarter_turns > 3 || (src_flags & ~MVHP_ORIENT_SRC_CODED) ||
+        (coded && !params_ok(p)) || ((uintptr_t)d_src & (coded ? 15 : 3)) || ((uintptr_t)d_yuv_out & 3) || ((uintptr_t)d_rgb_out & 3)) {
+        set_err("mvhp_orient_dev: invalid argument");
+        return MVHP_FAILURE;
+    }
+    if (((g->out_w | g->out_h) & 1u) || g->out_w < 2 || g->out_h < 2 || g->out_w > 16384 || g->out_h > 16384) {
+        set_err("mvhp_orient_dev: pictures of %u x %u (even sides of 2 to 16384)", g->out_w, g->out_h);
+        return MVHP_FAILURE;
+    }
+    mvhp::OrientArgs a;
+    a.w = (int)g->out_w;
+    a.h = (int)g->out_h;
+    if (coded) {
+        const uint32_t Wp = p->width_mbs * 16, Hp = p->height_mbs * 16;
+        if (((g->crop_x | g->crop_y | g->crop_w | g->crop_h) & 1u) || g->crop_w < 2 || g->crop_h < 2 || g->crop_x > Wp ||
+            g->crop_w > Wp - g->crop_x || g->crop_y > Hp || g->crop_h > Hp - g->crop_y || g->out_w != g->crop_w || g->out_h != g->crop_h) {
+            set_err("mvhp_orient_dev: rectangle %u,%u %ux%u -> %ux%u of a %ux%u picture (even, inside the picture, not scaled)",
+                    g->crop_x, g->crop_y, g->crop_w, g->crop_h, g->out_w, g->out_h, Wp, Hp);
+            return MVHP_FAILURE;
+        }
+        a.pitch = (int)Wp;
+        a.frame_bytes = mvhp_yuv_frame_bytes(p);
+        a.y_off = (size_t)g->crop_y * Wp + g->crop_x;
+        a.cb_off = (size_t)Wp * Hp + (size_t)(g->crop_y >> 1) * (Wp >> 1) + (g->crop_x >> 1);
+        a.cr_off = a.cb_off + (size_t)(Wp >> 1) * (Hp >> 1);
+    } else {
+        a.pitch = a.w;
+        a.frame_bytes = (size_t)a.w * a.h * 3 / 2;
+        a.y_off = 0;
+        a.cb_off = (size_t)a.w * a.h;
+        a.cr_off = a.cb_off + (size_t)(a.w >> 1) * (a.h >> 1);
+    }
+    if (n == 0 || (!d_yuv_out && !d_rgb_out)) return MVHP_SUCCESS;
+    HIP_TRY(hipSetDevice(c->device));
+    a.src = d_src;
+    a.src_end = d_src + (((size_t)n * a.frame_bytes) & ~(size_t)3);
+    a.turns = quarter_turns;
+    a.n = n;
+    a.yuv = d_yuv_out;
+    a.rgb = d_rgb_out;
+    // 0 and 2 turns, chroma rows per workgroup: the rule of the crop copy above (1 and 3 turns run in tiles)
+    int band = 8;
+    while (band > 1 && (double)n * ((a.h / 2 + band - 1) / band) < 4.0 * c->n_cus) band /= 2;
+    a.band = band;
+    HIP_TRY(mvhp::launch_orient(a, stream_of(c, stream)));
+    return MVHP_SUCCESS;
+}
+
 static int ensure(void **ptr, size_t *have, size_t need)
 {
     if (*have >= need) return MVHP_SUCCESS;
@@ -772,13 +824,14 @@ int eng_d2h(DevCtx *d, int n, void *const *dst, const void *const *src, const si
 }
 
 // One batch, on the context's stream inside one pair of events: expand, reconstruction (planes only when a resample pass or the
-// encoder follows, otherwise with fused RGB into d_rgb), the resample pass, the encoder, the picture scores; then one wait and one
+// encoder follows, otherwise with fused RGB into d_rgb), the resample pass, the turn, the encoder, the picture scores; then one wait and one
 // read of the error word.  (When the word is set the scores of that batch have been computed already: nothing reads them.)
 int eng_run_batch(DevCtx *d, const mvengine::BatchJob &j, mvengine::BatchDone &done, std::string &err)
 {
     mvhp_ctx *c = d->c;
     const mvhp_stream_params_t *p = j.params;
-    const bool resample = j.out_yuv || j.out_rgb;
+    const bool resample = j.out_yuv || j.out_rgb;   // (a pass behind the reconstruction writes them: the resample pass, the turn, or both)
+    if (j.turns < 0 || j.turns > 3 || (j.turns == 0 && j.mid_yuv) || (j.turns && !resample)) { err = "reconstruction: invalid orientation"; return MVHP_FAILURE; }
     if (!params_ok(p) || !j.d_compact || !j.d_packed || !j.d_yuv || j.n <= 0) { err = "reconstruction: invalid argument"; return MVHP_FAILURE; }
     if ((resample || j.jpeg) && !j.geom) { err = "reconstruction: no output geometry"; return MVHP_FAILURE; }
     if (j.jpeg && (!j.blob || !j.table || j.out_rgb)) { err = "reconstruction: invalid JPEG output"; return MVHP_FAILURE; }
@@ -789,7 +842,15 @@ int eng_run_batch(DevCtx *d, const mvengine::BatchJob &j, mvengine::BatchDone &d
     const bool deblock = (p->flags & MVHP_PARAM_DEBLOCK) != 0;
     int rc = (resample || j.jpeg) ? launch_all(c, p, j.d_packed, j.n, j.d_yuv, nullptr, c->stream, true, false, deblock)
                                   : launch_all(c, p, j.d_packed, j.n, j.d_yuv, j.d_rgb, c->stream, true, true, deblock);
-    if (rc == MVHP_SUCCESS && resample) rc = mvhp_resample_dev(c, p, j.geom, j.d_yuv, j.n, j.out_yuv, j.out_rgb, c->stream);
+    if (rc == MVHP_SUCCESS && resample && !j.turns) rc = mvhp_resample_dev(c, p, j.geom, j.d_yuv, j.n, j.out_yuv, j.out_rgb, c->stream);
+    if (rc == MVHP_SUCCESS && j.turns) {   // the geometry before the turn; planes of it first where the box scales
+        mvhp_output_geometry_t g0 = *j.geom;
+        if (j.turns & 1) std::swap(g0.out_w, g0.out_h);
+        if (j.mid_yuv) rc = mvhp_resample_dev(c, p, &g0, j.d_yuv, j.n, j.mid_yuv, nullptr, c->stream);
+        if (rc == MVHP_SUCCESS)
+            rc = mvhp_orient_dev(c, p, &g0, j.turns, j.mid_yuv ? 0u : MVHP_ORIENT_SRC_CODED, j.mid_yuv ? j.mid_yuv : j.d_yuv, j.n,
+                                 j.out_yuv, j.out_rgb, c->stream);
+    }
     if (rc == MVHP_SUCCESS && j.jpeg)
         rc = mvhp_jpeg_encode_dev(c, j.geom, j.jpeg, resample ? j.out_yuv : j.d_yuv, j.n, j.blob, j.blob_cap, j.table, c->stream);
     if (rc == MVHP_SUCCESS && j.stats) {
@@ -850,7 +911,7 @@ void eng_placed_free(DevCtx *d, void *arena)
 
 const mvengine::DeviceApi g_hip_api = {
     mvhp_device_count, mvhp_host_alloc, mvhp_host_free, eng_ctx_create, eng_ctx_destroy, eng_dev_alloc, eng_dev_free,
-    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE,
+    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT,
     eng_placed_alloc, eng_placed_free,
 };
 

@@ -106,6 +106,22 @@ hipError_t launch_resample(const ResampleArgs &a, hipStream_t stream);
 // crop only (ow == cw, oh == ch) as a copy from global memory to global memory (crop_copy.hip): the same bytes, no LDS, any width
 hipError_t launch_crop_copy(const ResampleArgs &a, hipStream_t stream);
 
+// display orientation (orient.hip): a rectangle of w x h of every source picture -> the picture turned by `turns` quarter turns
+// (clockwise), as planes and / or the RGB of the turned planes; the output is h x w for odd turns
+struct OrientArgs {
+    const uint8_t *src;          // n source pictures, frame_bytes apart, 4-byte aligned
+    const uint8_t *src_end;      // end of the last one, rounded down to a dword boundary (nothing behind it is read)
+    size_t         frame_bytes;
+    size_t         y_off, cb_off, cr_off;   // of the rectangle's first sample of each plane inside a source picture
+    int            pitch;        // of the source's luma plane (even; chroma: half of it)
+    int            w, h;         // the rectangle (even, at least 2)
+    int            turns;        // 0 .. 3
+    int            n;
+    int            band;         // 0 and 2 turns: chroma output rows per workgroup
+    uint8_t       *yuv, *rgb;    // n output pictures each, dense, 4-byte aligned; either may be NULL
+};
+hipError_t launch_orient(const OrientArgs &a, hipStream_t stream);
+
 // baseline JPEG from planar pictures (jpeg_encode.hip): DCT + quantisation, count, scans, write, headers
 struct JpegArgs {
     const uint8_t     *yuv;      // n pictures, planar Y | Cb | Cr of w x h

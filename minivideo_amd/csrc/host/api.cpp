@@ -250,13 +250,25 @@ std::vector<int> select_idrs(const mvhp_stream &s, int picture_number, int mode)
     return sel;
 }
 
-// ---- MINIVIDEO_CROP=1 / MINIVIDEO_THUMBNAIL=<w>x<h> (opt-in, include/minivideo.h): the output request of the decode call.
+// ---- MINIVIDEO_CROP=1 / MINIVIDEO_THUMBNAIL=<w>x<h> / MINIVIDEO_ROTATE=<auto or angle> (opt-in, include/minivideo.h): the output request of the decode call.
 // A box implies the crop.  false: a malformed value (the call fails before any device work; it is not ignored).
 bool output_request_from_env(mvhp_output_request_t &req, std::string &why)
 {
     memset(&req, 0, sizeof(req));
     if (const char *e = getenv("MINIVIDEO_CROP"))
         if (atoi(e) != 0) req.flags |= MVHP_OUTPUT_CROP;
+    // MINIVIDEO_ROTATE=auto|0|90|180|270 (opt-in): "auto" = the MP4's own display rotation, an angle = that many degrees
+    // clockwise whatever the file says; empty = unset
+    if (const char *r = getenv("MINIVIDEO_ROTATE")) {
+        if (!strcmp(r, "auto")) req.flags |= MVHP_OUTPUT_ORIENT;
+        else if (!strcmp(r, "90")) req.flags |= MVHP_OUTPUT_ROTATE(1);
+        else if (!strcmp(r, "180")) req.flags |= MVHP_OUTPUT_ROTATE(2);
+        else if (!strcmp(r, "270")) req.flags |= MVHP_OUTPUT_ROTATE(3);
+        else if (*r && strcmp(r, "0")) {
+            why = std::string("MINIVIDEO_ROTATE='") + r + "' is not auto, 0, 90, 180 or 270";
+            return false;
+        }
+    }
     const char *t = getenv("MINIVIDEO_THUMBNAIL");
     if (!t || !*t) return true;
     // decimal digits, 'x', decimal digits, nothing else; each side 2 ... 65535

@@ -141,6 +141,7 @@ enum BufKind {
     kRgb,        // fused RGB of the coded size
     kOutYuv,     // output pictures of a batch with a geometry (what is downloaded then)
     kOutRgb,
+    kMidYuv,     // a batch that scales AND turns: the resampled planes before the turn (the turn reads them, nothing downloads them)
     kJpegBlob,   // MVHP_OUT_JPEG: the encoder's blob (n x the raw picture) ...
     kJpegTab,    // ... and table of a batch
     kStats,      // MVHP_OUTPUT_SCORE: the records of a batch (n x 32 bytes)
@@ -179,9 +180,16 @@ struct Wants {
     bool yuv = true, rgb = false;   // which of them are downloaded (the planes are always reconstructed)
     bool jpeg = false;              // MVHP_OUT_JPEG: neither of them; JPEG files made on the device
     bool score = false;             // MVHP_OUTPUT_SCORE (it changes no picture and no path)
+    int turns = 0;                  // quarter turns the request applies (mvhp_output_turns): one value per call
 };
+// whether a batch of the DELIVERED geometry g, turned by `turns`, has a resample pass in front of the turn
+bool scales_before_turn(const mvhp_output_geometry_t &g, int turns)
+{
+    const uint32_t w = (turns & 1) ? g.out_h : g.out_w, h = (turns & 1) ? g.out_w : g.out_h;
+    return turns != 0 && (w != g.crop_w || h != g.crop_h);
+}
 // what a placed arena and the job's largest batch are planned for: pictures of the coded size, planes and RGB
-constexpr Wants kPlanesAndRgb = {true, true, false, false};
+constexpr Wants kPlanesAndRgb = {true, true, false, false, 0};
 
 // Device bytes per picture of one kind, for a batch of these parameters and this geometry (use_geom: it differs from the coded
 // size) in a call with these outputs; 0 = such a batch has no buffer of the kind.  The only place where the size of a batch
@@ -195,6 +203,7 @@ size_t picture_bytes(BufKind k, const mvhp_stream_params_t &p, const mvhp_output
     case kRgb:      return w.rgb && !use_geom ? mvhp_rgb_frame_bytes(&p) : 0;
     case kOutYuv:   return use_geom && (w.yuv || w.jpeg) ? mvhp_geometry_yuv_bytes(&g) : 0;
     case kOutRgb:   return use_geom && w.rgb ? mvhp_geometry_rgb_bytes(&g) : 0;
+    case kMidYuv:   return use_geom && scales_before_turn(g, w.turns) ? mvhp_geometry_yuv_bytes(&g) : 0;
     case kJpegBlob: return w.jpeg ? mvhp_geometry_yuv_bytes(&g) : 0;
     case kJpegTab:  return w.jpeg ? sizeof(mvhp_jpeg_entry_t) : 0;
     case kStats:    return w.score ? sizeof(mvhp_luma_stats_t) : 0;
@@ -450,7 +459,7 @@ bool Engine::picture_geometry(int idr, const mvhp_stream_params_t &p, mvhp_outpu
         g = mvhp_output_geometry_t{};
         return false;
     }
-    use = !same_geometry(g, coded_geometry(p));
+    use = w_.turns != 0 || !same_geometry(g, coded_geometry(p));   // (a turned picture of the coded size still has a pass)
     return true;
 }
 
@@ -554,6 +563,7 @@ bool Engine::ensure_devbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
     // sized for the batch at hand: geometries change inside a job, and these buffers are the small side of a batch.
     static const struct { const char *of, *unit; } what[kBufKinds] = {
         {"", " pictures"}, {"", " pictures"}, {"", " pictures"}, {"", " pictures"}, {"the output pictures of ", ""}, {"the output pictures of ", ""},
+        {"the unturned pictures of ", ""},
         {"the JPEG files of ", ""}, {"the JPEG files of ", ""}, {"the picture scores of ", ""}};
     const bool job_shape = bt.params.width_mbs == job_params_.width_mbs && bt.params.height_mbs == job_params_.height_mbs;
     for (int k = 0; k < kBufKinds; k++) {
@@ -949,6 +959,7 @@ void Engine::launcher(int k)
         else if (w_.score && !(api_.caps & CAP_SCORE)) err = "this device table has no picture-score operation";
         else if (w_.jpeg && !(api_.caps & CAP_JPEG)) err = "this device table has no JPEG operation";
         else if (b->use_geom && !w_.jpeg && !(api_.caps & CAP_GEOMETRY)) err = "this device table has no output-geometry operation";
+        else if (w_.turns && !(api_.caps & CAP_ORIENT)) err = "this device table has no orientation operation";
         else {
             auto buf = [&](BufKind k) { return need(*b, k) ? b->buf->m[k].p : nullptr; };   // (a buffer may hold an earlier batch's kind)
             BatchJob job{};
@@ -962,6 +973,8 @@ void Engine::launcher(int k)
             job.geom = b->use_geom || w_.jpeg ? &b->geom : nullptr;
             job.out_yuv = buf(kOutYuv);
             job.out_rgb = buf(kOutRgb);
+            job.turns = w_.turns;
+            job.mid_yuv = buf(kMidYuv);
             job.jpeg = w_.jpeg ? &jpeg_ : nullptr;
             job.blob = buf(kJpegBlob);
             job.blob_cap = (size_t)b->total * need(*b, kJpegBlob);
@@ -1191,7 +1204,7 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
                    mvhp_picture_sink_t sink, mvhp_picture_sink_ex_t sink_ex, void *user, mvhp_decode_stats_t *stats,
                    std::string &err)
 {
-    if (req && ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_SCORE)) || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2)))) {
+    if (req && ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_SCORE | MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK)) || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2)))) {
         err = "malformed output request (box sides must be at least 2)";
         return MVHP_FAILURE;
     }
@@ -1219,6 +1232,8 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         req_ = req ? *req : mvhp_output_request_t{};
         w_.score = (req_.flags & MVHP_OUTPUT_SCORE) != 0;
         req_.flags &= ~MVHP_OUTPUT_SCORE;   // (what is left decides the geometry: none = the path of a call without a request)
+        w_.turns = mvhp_output_turns(&s, &req_);
+        if (w_.turns == 0) req_.flags &= ~(MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK);   // (turns that come to 0: today's paths exactly)
         stop_ = false; sink_waiting_ = false;
         pos_ = issued_ = consumed_ = ok_ = failed_ = 0;
         next_batch_id_ = 0;

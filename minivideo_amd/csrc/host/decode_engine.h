@@ -32,8 +32,12 @@ struct BatchJob {
     uint8_t *d_rgb;   // fused RGB of the coded size, or NULL.  Only without a resample pass and without JPEG: those reconstruct
                       // planes only, without the fused colour epilogue
     const mvhp_output_geometry_t *geom;   // of the n pictures; NULL: the coded size, nothing below but `stats` may be set
-    uint8_t *out_yuv, *out_rgb;   // mvhp_resample_dev of d_yuv into n pictures of `geom`: planes and / or RGB (either may be NULL);
+    uint8_t *out_yuv, *out_rgb;   // (turns 0) mvhp_resample_dev of d_yuv into n pictures of `geom`: planes and / or RGB (either may be NULL);
                                   // both NULL: no resample pass (only with `jpeg`: files of the coded size, geom names that size)
+    int turns;          // quarter turns (1..3; 0: none, mid_yuv NULL).  `geom` is then the geometry DELIVERED (out_w / out_h exchanged for
+    uint8_t *mid_yuv;   // odd turns) and out_yuv / out_rgb hold the turned pictures: mvhp_orient_dev straight from the crop rectangle
+                        // of d_yuv where nothing scales (mid_yuv NULL), else mvhp_resample_dev of d_yuv into mid_yuv (planes of the
+                        // geometry before the turn) and mvhp_orient_dev of those
     const mvhp_jpeg_params_t *jpeg;   // NULL: no encoder.  Else mvhp_jpeg_encode_dev of the n pictures of `geom` -- out_yuv where a
                                       // resample pass ran, else d_yuv -- into `blob` (blob_cap bytes) and `table` (n entries)
     uint8_t *blob; size_t blob_cap; mvhp_jpeg_entry_t *table;
@@ -46,7 +50,7 @@ struct BatchDone {
 };
 
 // what run_batch can do beyond pictures of the coded size; a job that needs a missing bit fails in the engine, with a message
-enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4 };
+enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4, CAP_ORIENT = 8 };
 
 // Every operation blocks its calling thread until the device has finished it; the engine runs one thread per queue
 // and context, which is what overlaps upload(k+1), kernel(k) and download(k-1).  *ms = device-side duration.

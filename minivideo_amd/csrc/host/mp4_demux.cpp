@@ -189,6 +189,25 @@ void build_samples(const Tables &tb, size_t file_size, VideoTrack &t)
         if (n >= 1 && (size_t)(n - 1) < t.samples.size()) t.samples[n - 1].sync = true;
 }
 
+// The display matrix of a tkhd box {a, b, u; c, d, v; x, y, w} (16.16 fixed point, u v w 2.30) as clockwise quarter turns.  Only
+// the four pure rotations count; mirrors, scales, shears, a w other than 1.0 and non-zero u / v give 0, as does a box too short
+// to hold the matrix.  The translation x, y is ignored: muxers set it either way.
+int tkhd_quarter_turns(const Reader &r, const Box &b)
+{
+    if (b.body + 1 > b.end) return 0;
+    const size_t m = b.body + (r.u8(b.body) == 1 ? 52 : 40);
+    if (m + 36 > b.end) return 0;
+    uint32_t w[9];
+    for (int i = 0; i < 9; i++) w[i] = r.u32(m + 4 * (size_t)i);
+    if (w[2] != 0 || w[5] != 0 || w[8] != 0x40000000u) return 0;
+    const uint32_t one = 0x00010000u, neg = 0xFFFF0000u;
+    const uint32_t a = w[0], bb = w[1], c = w[3], d = w[4];
+    if (a == 0 && bb == one && c == neg && d == 0) return 1;
+    if (a == neg && bb == 0 && c == 0 && d == neg) return 2;
+    if (a == 0 && bb == neg && c == one && d == 0) return 3;
+    return 0;
+}
+
 void parse_trak(const Reader &r, const Box &trak, VideoTrack &out)
 {
     VideoTrack t;
@@ -197,7 +216,8 @@ void parse_trak(const Reader &r, const Box &trak, VideoTrack &out)
     Box b;
     size_t p = trak.body;
     while (next_box(r, p, trak.end, b)) {
-        if (b.type == fourcc("mdia")) {
+        if (b.type == fourcc("tkhd")) t.quarter_turns = tkhd_quarter_turns(r, b);
+        else if (b.type == fourcc("mdia")) {
             Box m;
             size_t q = b.body;
             while (next_box(r, q, b.end, m)) {

@@ -1,7 +1,7 @@
 // mp4_demux.h -- minimal ISO-BMFF reader for the IDR thumbnail path (SURVEY.md 8f "next" row f1):
 // finds the first H.264 video track, its avcC parameter sets and its sample table.  Restates the parts of
 // demuxer/mp4/mp4.c the decode path depends on: box walk (:633-692, :895-949, :1244-1310, :1377-1427, :1503-1625),
-// stsd/avc1/avcC (:1627-1939), stss (:2301), stsc (:2362), stsz (:2448), stco/co64 (:2527) and the sample-map
+// stsd/avc1/avcC (:1627-1939), tkhd matrix (:1167-1197, which traces and drops it), stss (:2301), stsc (:2362), stsz (:2448), stco/co64 (:2527) and the sample-map
 // construction of convertTrack (:150-500).
 #pragma once
 #include <stddef.h>
@@ -26,6 +26,8 @@ struct VideoTrack {
     unsigned width = 0, height = 0;
     uint32_t timescale = 0;
     uint64_t duration = 0;
+    int  quarter_turns = 0;                           // tkhd matrix: clockwise quarter turns for display, 0..3 (pure rotations
+                                                      // only; a mirrored, scaled or sheared matrix gives 0)
     std::vector<NalRef> sps, pps;                     // inside the avcC box
     std::vector<Sample> samples;                      // decoding order
 };

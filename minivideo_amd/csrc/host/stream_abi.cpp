@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../hip/resample_taps.h"
@@ -89,6 +90,7 @@ int mvhp_stream::build_mp4(std::string &err)
 {
     mp4::VideoTrack trk;
     if (!mp4::parse(data, size, trk, err)) return RC_FAILURE;
+    quarter_turns = trk.quarter_turns;
     Sps sps_tab[32];
     Pps pps_tab[256];
     std::vector<uint8_t> rbsp;
@@ -236,6 +238,8 @@ MVHP_EXPORT void mvhp_stream_close(mvhp_stream_t *s) { delete s; }
 
 MVHP_EXPORT int mvhp_stream_idr_count(const mvhp_stream_t *s) { return s ? (int)s->idrs.size() : 0; }
 
+MVHP_EXPORT int mvhp_stream_rotation(const mvhp_stream_t *s) { return s ? 90 * (s->quarter_turns & 3) : 0; }
+
 MVHP_EXPORT int mvhp_stream_params(const mvhp_stream_t *s, int idr, mvhp_stream_params_t *out)
 {
     if (!s || !out || idr < 0 || (size_t)idr >= s->idrs.size() || !s->idrs[idr].ok) return MVHP_FAILURE;
@@ -293,8 +297,31 @@ MVHP_EXPORT int mvhp_geometry_fit(uint32_t cw, uint32_t ch, uint32_t bw, uint32_
     return MVHP_SUCCESS;
 }
 
-MVHP_EXPORT int mvhp_output_geometry(const mvhp_stream_t *s, int idr, const mvhp_output_request_t *req, mvhp_output_geometry_t *out)
+MVHP_EXPORT int mvhp_output_turns(const mvhp_stream_t *s, const mvhp_output_request_t *req)
 {
+    if (!req) return 0;
+    const int own = (s && (req->flags & MVHP_OUTPUT_ORIENT)) ? s->quarter_turns : 0;
+    return (own + (int)((req->flags & MVHP_OUTPUT_ROTATE_MASK) >> MVHP_OUTPUT_ROTATE_SHIFT)) & 3;
+}
+
+MVHP_EXPORT int mvhp_output_geometry(const mvhp_stream_t *s, int idr, const mvhp_output_request_t *req_in, mvhp_output_geometry_t *out)
+{
+    // the turn: the geometry is formed in the coded picture's orientation -- for odd turns against the box turned back -- and the
+    // sides of the output are exchanged afterwards; crop_* stay coded coordinates.  Zero turns: the request without these bits
+    const int turns = mvhp_output_turns(s, req_in);
+    mvhp_output_request_t unturned;
+    const mvhp_output_request_t *req = req_in;
+    if (req_in && (req_in->flags & (MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK))) {
+        unturned = *req_in;
+        unturned.flags &= ~(MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK);
+        if (turns & 1) std::swap(unturned.box_w, unturned.box_h);
+        req = &unturned;
+        if (out && (turns & 1)) {
+            const int rc = mvhp_output_geometry(s, idr, req, out);
+            if (rc == MVHP_SUCCESS) std::swap(out->out_w, out->out_h);
+            return rc;
+        }
+    }
     if (!req || req->flags == 0) {   // the coded size
         mvhp_stream_params_t p;
         if (!out || mvhp_stream_params(s, idr, &p) != MVHP_SUCCESS) {

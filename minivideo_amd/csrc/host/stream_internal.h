@@ -21,6 +21,7 @@ struct mvhp_stream {
     std::vector<Idr> idrs;
     int param_errors = 0;
     bool spec = false;            // MVHP_STREAM_SPEC: standard-conformant index + luma-DC rule (opt-in, outside parity)
+    int quarter_turns = 0;        // MP4: clockwise quarter turns of the video track's tkhd matrix (0 for Annex B)
     bool deblock = false;         // MVHP_STREAM_DEBLOCK: records carry the deblocking fields, params ask for the filter
 
     int build(std::string &err);      // Annex-B elementary stream

@@ -53,6 +53,22 @@ class StreamParams(C.Structure):
 
 OUT_JPEG = 4                                                            # mvhp_engine_decode_ex output kind (MVHP_OUT_JPEG)
 OUTPUT_CROP, OUTPUT_BOX, OUTPUT_SCORE = 1, 2, 4                          # mvhp_output_request_t flags (MVHP_OUTPUT_*)
+OUTPUT_ORIENT, OUTPUT_ROTATE_SHIFT = 8, 4                                # ... the stream's own rotation; bits 4-5: further turns
+ORIENT_SRC_CODED = 1                                                    # mvhp_orient_dev src_flags (MVHP_ORIENT_SRC_CODED)
+
+
+def rotate_flags(rotate):
+    """None -> 0; "auto" -> MVHP_OUTPUT_ORIENT; 0 / 90 / 180 / 270 -> MVHP_OUTPUT_ROTATE(quarter turns); ("auto", angle) -> both:
+    the angle on top of the stream's own rotation"""
+    if rotate is None:
+        return 0
+    if isinstance(rotate, tuple):
+        return rotate_flags(rotate[0]) | rotate_flags(rotate[1])
+    if rotate == "auto":
+        return OUTPUT_ORIENT
+    if rotate not in (0, 90, 180, 270):
+        raise ValueError('rotate must be "auto", 0, 90, 180 or 270')
+    return (int(rotate) // 90) << OUTPUT_ROTATE_SHIFT
 
 
 class OutputGeometry(C.Structure):
@@ -79,14 +95,16 @@ class OutputRequest(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("box_w", C.c_uint32), ("box_h", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-def output_request(output):
-    """None -> None (the coded size); "crop" -> the SPS crop; (w, h) -> the crop fitted into a w x h box"""
+def output_request(output, rotate=None):
+    """None -> None (the coded size); "crop" -> the SPS crop; (w, h) -> the crop fitted into a w x h box.  rotate (see
+    rotate_flags()) adds the orientation bits; with rotate given the result is never None"""
+    rot = rotate_flags(rotate)
     if output is None:
-        return None
+        return OutputRequest(rot, 0, 0, 0) if rotate is not None else None
     if output == "crop":
-        return OutputRequest(OUTPUT_CROP, 0, 0, 0)
+        return OutputRequest(OUTPUT_CROP | rot, 0, 0, 0)
     w, h = output
-    return OutputRequest(OUTPUT_CROP | OUTPUT_BOX, int(w), int(h), 0)
+    return OutputRequest(OUTPUT_CROP | OUTPUT_BOX | rot, int(w), int(h), 0)
 
 
 class JpegParams(C.Structure):
@@ -161,10 +179,21 @@ def stream_crop(stream_handle, idr):
     return g if lib().mvhp_stream_crop(stream_handle, int(idr), C.byref(g)) == SUCCESS else None
 
 
-def output_geometry(stream_handle, idr, output):
-    """mvhp_output_geometry under output_request(output), or None"""
+def stream_rotation(stream_handle):
+    """mvhp_stream_rotation: the display rotation of an MP4's video track, clockwise, 0 / 90 / 180 / 270 (Annex B: 0)"""
+    return int(lib().mvhp_stream_rotation(stream_handle))
+
+
+def output_turns(stream_handle, output=None, rotate=None):
+    """mvhp_output_turns: the quarter turns (0 .. 3) output_request(output, rotate) applies to pictures of the stream"""
+    req = output_request(output, rotate)
+    return int(lib().mvhp_output_turns(stream_handle, C.byref(req) if req is not None else None))
+
+
+def output_geometry(stream_handle, idr, output, rotate=None):
+    """mvhp_output_geometry under output_request(output, rotate), or None: what the sink gets"""
     g = OutputGeometry()
-    req = output_request(output)
+    req = output_request(output, rotate)
     rc = lib().mvhp_output_geometry(stream_handle, int(idr), C.byref(req) if req is not None else None, C.byref(g))
     return g if rc == SUCCESS else None
 
@@ -248,6 +277,12 @@ def lib():
         getattr(L, f).argtypes = [pg]
     L.mvhp_resample_dev.restype = i32
     L.mvhp_resample_dev.argtypes = [vp, pp, pg, vp, i32, vp, vp, vp]
+    L.mvhp_orient_dev.restype = i32
+    L.mvhp_orient_dev.argtypes = [vp, pp, pg, i32, u32, vp, i32, vp, vp, vp]
+    L.mvhp_stream_rotation.restype = i32
+    L.mvhp_stream_rotation.argtypes = [vp]
+    L.mvhp_output_turns.restype = i32
+    L.mvhp_output_turns.argtypes = [vp, C.POINTER(OutputRequest)]
     L.mvhp_luma_score.restype = C.c_uint32
     L.mvhp_luma_score.argtypes = [C.POINTER(LumaStats)]
     L.mvhp_blank_choose.restype = i32
@@ -364,6 +399,16 @@ class HotPath:
         rc = self._L.mvhp_resample_dev(self._h, C.byref(params), C.byref(geom), d_yuv_coded, int(n), d_yuv_out, d_rgb_out, stream)
         if rc != SUCCESS:
             raise _err(self._L, "mvhp_resample_dev")
+
+    def orient_dev(self, params, geom, quarter_turns, d_src, n, d_yuv_out=None, d_rgb_out=None, coded=True, stream=None):
+        """n pictures (device) turned by quarter_turns (0 .. 3, clockwise) into planes and / or RGB (device).  geom is the
+        geometry BEFORE the turn; coded=True: d_src holds coded pictures of `params` and geom's crop rectangle is read out of
+        them (out size = crop size); coded=False: d_src holds dense pictures of geom.out_w x geom.out_h (params may be None).
+        Output pictures are out_h x out_w for odd turns.  Asynchronous."""
+        rc = self._L.mvhp_orient_dev(self._h, C.byref(params) if params is not None else None, C.byref(geom), int(quarter_turns),
+                                     ORIENT_SRC_CODED if coded else 0, d_src, int(n), d_yuv_out, d_rgb_out, stream)
+        if rc != SUCCESS:
+            raise _err(self._L, "mvhp_orient_dev")
 
     def luma_stats_dev(self, params, geom, d_yuv_coded, n, d_stats, stream=None):
         """n coded pictures (device) -> n LumaStats records (LUMA_STATS_DTYPE, device) over geom's crop rectangle.  Asynchronous."""
@@ -535,7 +580,7 @@ class Engine:
         self._L.mvhp_engine_release_picture(self._h, int(seq))
 
     def decode(self, stream_handle, order, wanted=None, want_rgb=False, sink=None, output=None, jpeg=None, restart_mcus=0,
-               score=False):
+               score=False, rotate=None):
         """sink(seq, idr, rc, err, params, yuv ndarray | None, rgb ndarray | None) -> 1 accept / 0 reject / -1 stop /
         2 accept and keep until release_picture(seq); the arrays are views of page-locked memory valid only during the call
         (or until the release).  Returns (rc, stats dict).
@@ -546,12 +591,14 @@ class Engine:
         device and only the files come back: sink(seq, idr, rc, err, params, geometry, None, file bytes as a uint8 array);
         want_rgb is ignored; restart_mcus 0 = one MCU row.
         score=True: MVHP_OUTPUT_SCORE -- the sink is called as for `output` (with the geometry, also for pictures of the coded
-        size) and finds each picture's score in geometry.score; the pictures are the same bytes."""
+        size) and finds each picture's score in geometry.score; the pictures are the same bytes.
+        rotate = "auto" (the stream's own rotation, stream_rotation()) or 0 / 90 / 180 / 270 (clockwise): the pictures are
+        turned on the device; the sink is called as for `output`, and its geometry is the one of the turned picture."""
         order = (C.c_int * len(order))(*order)
         st = DecodeStats()
         n_wanted = len(order) if wanted is None else wanted
-        if output is not None or jpeg is not None or score:
-            req = output_request(output) or OutputRequest(0, 0, 0, 0)
+        if output is not None or jpeg is not None or score or rotate is not None:
+            req = output_request(output, rotate) or OutputRequest(0, 0, 0, 0)
             if score:
                 req.flags |= OUTPUT_SCORE
             if jpeg is not None:

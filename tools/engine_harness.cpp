@@ -4,10 +4,11 @@
 // lets the sink check that the right picture arrives in the right place, in order, through chunks, batches, several
 // contexts and a re-queue.  Nothing here is part of libminivideo.so.
 //
-// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes> [jpeg | score]]]
+// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes> [jpeg | score | orient]]]
 // The fourth argument adds the geometry mode: mvhp_engine_decode_ex and minivideo_decode under MINIVIDEO_CROP /
 // MINIVIDEO_THUMBNAIL against the stub's resample targets.  A fifth argument adds the JPEG mode (MVHP_OUT_JPEG) or the
-// score mode (MVHP_OUTPUT_SCORE against the stub's picture scores, which sum the stub's coded planes on the CPU).
+// score mode (MVHP_OUTPUT_SCORE against the stub's picture scores, which sum the stub's coded planes on the CPU), or the orient
+// mode (MVHP_OUTPUT_ORIENT / MVHP_OUTPUT_ROTATE and MINIVIDEO_ROTATE against the stub's turn).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -132,9 +133,12 @@ mvhp_luma_stats_t expected_stats(uint64_t h, bool pattern, const mvhp_stream_par
 // * JPEG: the coded planes (and the output planes of a batch with a resample pass) are written in full, and every picture gets a
 //   "file" whose length depends on its records -- 32 + checksum % (half the raw picture) bytes of 0x3c, the checksum in bytes 0-7,
 //   0x79 last -- at the next multiple of 16 of the blob; a picture whose checksum is a multiple of 5 is reported too big;
+// * turns (orient mode): the outputs are stamped as resample targets are -- `geom` is the delivered geometry, so the output buffers
+//   must hold n pictures of it -- and a batch that scales before the turn must bring the buffer of the unturned planes, which is
+//   written in full, and no other batch may bring one;
 // * scores: honest sums over the rectangle of the coded planes the batch buffer holds.
 constexpr uint8_t kLastYuv = 0x77, kLastRgb = 0x78, kLastJpeg = 0x79;
-std::atomic<int> g_jpeg_calls{0}, g_stats_calls{0};
+std::atomic<int> g_jpeg_calls{0}, g_stats_calls{0}, g_orient_calls{0}, g_mid_calls{0};
 size_t stub_jpeg_length(uint64_t h, size_t raw) { return 32 + (size_t)(h % (raw / 2)); }
 bool stub_jpeg_too_big(uint64_t h) { return h % 5 == 0; }
 int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &done, std::string &err)
@@ -144,9 +148,16 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
     const bool resample = j.out_yuv || j.out_rgb;
     (j.jpeg ? g_jpeg_calls : resample ? g_geometry_calls : g_recon_calls)++;
     if (!j.d_yuv || (!j.jpeg && (g != nullptr) != resample)) { err = "stub: geometry launch without buffers"; return MVHP_FAILURE; }
+    if (j.turns < 0 || j.turns > 3 || (!j.turns && j.mid_yuv) || (j.turns && (!g || !resample))) { err = "stub: orientation without buffers"; return MVHP_FAILURE; }
+    if (j.turns) {
+        const uint32_t w0 = (j.turns & 1) ? g->out_h : g->out_w, h0 = (j.turns & 1) ? g->out_w : g->out_h;   // before the turn
+        if ((j.mid_yuv != nullptr) != (w0 != g->crop_w || h0 != g->crop_h)) { err = "stub: the unturned planes exactly where the batch scales"; return MVHP_FAILURE; }
+        if (j.mid_yuv) { memset(j.mid_yuv, 0x13, (size_t)j.n * mvhp_geometry_yuv_bytes(g)); g_mid_calls++; }
+        g_orient_calls++;
+    }
     // (JPEG: a resample pass exactly where the pictures are not of the coded size)
     if (j.jpeg && (!g || !j.blob || !j.table || j.out_rgb || j.jpeg->quality < 1 || j.jpeg->quality > 100 ||
-                   (j.out_yuv != nullptr) != (g->out_w != p->width_mbs * 16 || g->out_h != p->height_mbs * 16))) {
+                   (j.out_yuv != nullptr) != (j.turns != 0 || g->out_w != p->width_mbs * 16 || g->out_h != p->height_mbs * 16))) {
         err = "stub: JPEG launch without buffers or parameters";
         return MVHP_FAILURE;
     }
@@ -222,7 +233,7 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
 
 mvengine::DeviceApi g_stub = {stub_device_count, stub_host_alloc, stub_host_free, stub_ctx_create, stub_ctx_destroy,
                                     stub_dev_alloc, stub_dev_free, stub_dev_free_bytes, stub_copy_n, stub_copy_n, stub_run_batch,
-                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE,
+                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT,
                                     nullptr, nullptr};   // (no placed arena on the stub device)
 
 uint64_t picture_checksum(const mvhp_stream &s, int idr)
@@ -273,6 +284,54 @@ struct CheckG {
             if (!rgb) { c.bad++; return 0; }
             memcpy(&got, rgb + 8, 8);
             if (got != h || rgb[0] != 0xa5 || rgb[gr - 1] != (coded ? 0xa5 : kLastRgb)) c.bad++;
+        } else if (rgb) c.bad++;
+        c.ok++;
+        return 1;
+    }
+};
+
+// sink of the orient mode: the geometry is the one mvhp_output_geometry announces for the request (the turned one), the buffers are
+// sized by it, and every picture of a call that turns went through a pass (the stub's last-byte stamps)
+struct CheckO {
+    const mvhp_stream *s = nullptr;
+    mvhp_output_request_t req{};
+    bool want_yuv = true, want_rgb = false;
+    int calls = 0, ok = 0, failed = 0, bad = 0, next_seq = 0, no_op = 0;
+    uint64_t bytes = 0;
+    std::vector<int> order;
+    static int sink(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                    const uint8_t *yuv, const uint8_t *rgb)
+    {
+        CheckO &c = *static_cast<CheckO *>(user);
+        c.calls++;
+        if (seq != c.next_seq || idr != c.order[(size_t)seq] || !g) c.bad++;
+        c.next_seq = seq + 1;
+        mvhp_output_geometry_t want;
+        const bool formed = mvhp_output_geometry(c.s, idr, &c.req, &want) == MVHP_SUCCESS;
+        if (rc != MVHP_SUCCESS) {
+            c.failed++;
+            if (err && strstr(err, "no orientation operation")) c.no_op++;
+            else if (!err || !*err || yuv || rgb || formed) c.bad++;
+            return 0;
+        }
+        if (!formed || !g || memcmp(&want, g, sizeof(want)) != 0) { c.bad++; return 0; }
+        const int turns = mvhp_output_turns(c.s, &c.req);
+        const bool coded = turns == 0 && g->crop_x == 0 && g->crop_y == 0 && g->out_w == p->width_mbs * 16 && g->out_h == p->height_mbs * 16 &&
+                           g->crop_w == g->out_w && g->crop_h == g->out_h;
+        const uint64_t h = picture_checksum(*c.s, idr);
+        const size_t gy = mvhp_geometry_yuv_bytes(g), gr = mvhp_geometry_rgb_bytes(g);
+        uint64_t got = 0;
+        if (c.want_yuv) {
+            if (!yuv) { c.bad++; return 0; }
+            memcpy(&got, yuv, 8);
+            if (got != h || yuv[8] != 0x5a || yuv[gy - 1] != (coded ? 0x5a : kLastYuv)) c.bad++;
+            c.bytes += gy;
+        } else if (yuv) c.bad++;
+        if (c.want_rgb) {
+            if (!rgb) { c.bad++; return 0; }
+            memcpy(&got, rgb + 8, 8);
+            if (got != h || rgb[0] != 0xa5 || rgb[gr - 1] != (coded ? 0xa5 : kLastRgb)) c.bad++;
+            c.bytes += gr;
         } else if (rgb) c.bad++;
         c.ok++;
         return 1;
@@ -924,6 +983,222 @@ int main(int argc, char **argv)
                 mvhp_engine_destroy(e);
             }
             printf("JPEG MODE DONE\n");
+        }
+        if (argc > 5 && !strcmp(argv[5], "orient")) {   // ---- orient mode: MVHP_OUTPUT_ORIENT / _ROTATE against the stub's turn ----
+            auto run_o = [&](const char *name, mvhp_engine_opts_t o, const mvhp_stream &st, const std::vector<int> &order, int mask,
+                             const mvhp_output_request_t &req, CheckO &c, mvhp_decode_stats_t &stats) {
+                mvhp_engine_t *e = nullptr;
+                if (mvhp_engine_create(&o, &e) != MVHP_SUCCESS) { failures++; return MVHP_FAILURE; }
+                c.s = &st; c.req = req; c.order = order;
+                c.want_rgb = (mask & 1) != 0;
+                c.want_yuv = !c.want_rgb || (mask & 2) == 0;
+                const int rc = mvhp_engine_decode_ex(e, &st, order.data(), (int)order.size(), (int)order.size(), mask, &req, CheckO::sink, &c, &stats);
+                mvhp_engine_destroy(e);
+                printf("%-28s flags=%#x rc=%d ok=%u failed=%u batches=%u geometry=%u requeued=%u d2h=%llu\n", name, req.flags, rc, stats.pictures_ok,
+                       stats.pictures_failed, stats.batches, stats.geometry_launches, stats.batches_requeued, (unsigned long long)stats.d2h_bytes);
+                return rc;
+            };
+            // runs of equal delivered geometry are batches; those that scale before the turn bring the extra buffer
+            auto expect_o = [&](const std::vector<int> &order, const mvhp_output_request_t &req, int &runs, int &scaled_runs, int &unformed) {
+                runs = scaled_runs = unformed = 0;
+                mvhp_output_geometry_t prev{};
+                bool have = false;
+                const int turns = mvhp_output_turns(&s3, &req);
+                for (int idr : order) {
+                    mvhp_output_geometry_t g;
+                    if (mvhp_output_geometry(&s3, idr, &req, &g) != MVHP_SUCCESS) { unformed++; continue; }
+                    if (!have || memcmp(&prev, &g, sizeof(g)) != 0) {
+                        runs++;
+                        const uint32_t w0 = (turns & 1) ? g.out_h : g.out_w, h0 = (turns & 1) ? g.out_w : g.out_h;
+                        if (w0 != g.crop_w || h0 != g.crop_h) scaled_runs++;
+                    }
+                    prev = g;
+                    have = true;
+                }
+            };
+            int scaled_seen = 0, unscaled_seen = 0;
+            for (uint32_t q = 1; q <= 3; q++)
+                for (uint32_t shape : {0u, (uint32_t)MVHP_OUTPUT_CROP, (uint32_t)(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX)})
+                    for (int mask : {0, MVHP_OUT_RGB, MVHP_OUT_RGB_ONLY}) {
+                        const mvhp_output_request_t req{shape | MVHP_OUTPUT_ROTATE(q), 40, 24, 0};   // (an oblong box: turned, it is another box)
+                        mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 64;
+                        CheckO c; mvhp_decode_stats_t st;
+                        int runs, scaled_runs, unformed;
+                        expect_o(o3, req, runs, scaled_runs, unformed);
+                        const int orient0 = g_orient_calls, mid0 = g_mid_calls;
+                        EXPECT(run_o("orient", o, s3, o3, mask, req, c, st) == MVHP_SUCCESS);
+                        EXPECT(c.bad == 0 && c.calls == n3 && c.failed == unformed && c.ok == n3 - unformed);
+                        // every batch of a call that turns has the pass and counts as a geometry launch; the buffer of the unturned
+                        // planes exists exactly in the batches that scale
+                        // (the turn alone forms one geometry per picture size, and a batch also ends where the stream parameters change)
+                        EXPECT(shape == 0 ? (int)st.batches >= runs : (int)st.batches == runs);
+                        EXPECT(st.geometry_launches == st.batches && g_orient_calls - orient0 == (int)st.batches);
+                        EXPECT(shape == 0 ? scaled_runs == 0 && g_mid_calls == mid0 : g_mid_calls - mid0 == scaled_runs);
+                        EXPECT(st.d2h_bytes == c.bytes);   // the turned pictures only
+                        scaled_seen += scaled_runs;
+                        unscaled_seen += runs - scaled_runs;
+                    }
+            EXPECT(scaled_seen > 0 && unscaled_seen > 0);
+            {   // odd turns exchange the sides of what is delivered, and the box is applied to the turned picture
+                const mvhp_output_request_t r0{MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX, 40, 24, 0}, r1{MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_ROTATE(1), 24, 40, 0};
+                int swapped = 0;
+                for (int idr = 0; idr < n3; idr++) {
+                    mvhp_output_geometry_t a, b;
+                    if (mvhp_output_geometry(&s3, idr, &r0, &a) != MVHP_SUCCESS) continue;
+                    EXPECT(mvhp_output_geometry(&s3, idr, &r1, &b) == MVHP_SUCCESS);
+                    EXPECT(a.out_w == b.out_h && a.out_h == b.out_w && a.crop_x == b.crop_x && a.crop_y == b.crop_y && a.crop_w == b.crop_w && a.crop_h == b.crop_h);
+                    EXPECT(mvhp_geometry_yuv_bytes(&a) == mvhp_geometry_yuv_bytes(&b));
+                    swapped++;
+                }
+                EXPECT(swapped >= 4);
+            }
+            {   // turns that come to 0 -- no angle, "auto" on a stream without a rotation -- take today's paths: no turn, no extra buffer, and
+                // where the pictures are of the coded size no geometry launch either
+                const int orient0 = g_orient_calls, mid0 = g_mid_calls, geom0 = g_geometry_calls;
+                for (const mvhp_output_request_t &req : {mvhp_output_request_t{MVHP_OUTPUT_ROTATE(0), 0, 0, 0}, mvhp_output_request_t{MVHP_OUTPUT_ORIENT, 0, 0, 0},
+                                                         mvhp_output_request_t{MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX, 4096, 4096, 0}}) {
+                    mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 3; o.batch_pictures = 7;
+                    CheckO c; mvhp_decode_stats_t st;
+                    EXPECT(run_o("orient: zero turns", o, s, all, MVHP_OUT_RGB, req, c, st) == MVHP_SUCCESS);
+                    EXPECT(c.bad == 0 && c.ok == n_idr && st.geometry_launches == 0);
+                }
+                EXPECT(g_orient_calls == orient0 && g_mid_calls == mid0 && g_geometry_calls == geom0);
+                // ... and with a crop the launches of the request without the flag
+                const mvhp_output_request_t with{MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_CROP, 0, 0, 0};
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 64;
+                CheckO c; CheckG cg; mvhp_decode_stats_t st, stg;
+                EXPECT(run_o("orient: zero turns, crop", o, s3, o3, MVHP_OUT_RGB, with, c, st) == MVHP_SUCCESS && c.bad == 0);
+                EXPECT(run_ex("the same without the flag", o, s3, o3, MVHP_OUT_RGB, crop, cg, stg) == MVHP_SUCCESS && cg.bad == 0);
+                EXPECT(st.batches == stg.batches && st.geometry_launches == stg.geometry_launches && st.d2h_bytes == stg.d2h_bytes);
+                EXPECT(g_orient_calls == orient0 && g_mid_calls == mid0);
+            }
+            {   // small batches, three contexts, the first batch of context 0 fails: re-queued with its turn
+                std::vector<int> order;
+                for (int k = 0; k < 3 * n3; k++) order.push_back(k % n3);
+                const mvhp_output_request_t req{MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_ROTATE(3), 40, 24, 0};
+                mvhp_engine_opts_t o = base; o.contexts = 3; o.chunk_pictures = 2; o.batch_pictures = 3; o.fail_context = 0;
+                CheckO c; mvhp_decode_stats_t st;
+                int runs, scaled_runs, unformed;
+                expect_o(order, req, runs, scaled_runs, unformed);
+                EXPECT(run_o("orient requeue/3ctx", o, s3, order, MVHP_OUT_RGB, req, c, st) == MVHP_SUCCESS);
+                EXPECT(c.bad == 0 && c.failed == unformed && c.ok == (int)order.size() - unformed && st.batches_requeued == 1);
+                EXPECT((int)st.batches >= runs && st.d2h_bytes == c.bytes);
+            }
+            {   // JPEG of turned pictures: the encoder reads the turned planes, the blob is sized by the delivered geometry
+                const mvhp_output_request_t req{MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_ROTATE(1), 40, 24, MVHP_JPEG_REQUEST(80, 0)};
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 5;
+                mvhp_engine_t *e = nullptr;
+                EXPECT(mvhp_engine_create(&o, &e) == MVHP_SUCCESS);
+                CheckJ c; mvhp_decode_stats_t st;
+                c.s = &s3; c.req = req; c.order = o3;
+                const int orient0 = g_orient_calls;
+                EXPECT(mvhp_engine_decode_ex(e, &s3, o3.data(), n3, n3, MVHP_OUT_JPEG, &req, CheckJ::sink, &c, &st) == MVHP_SUCCESS);
+                mvhp_engine_destroy(e);
+                printf("%-28s ok=%d failed=%d batches=%u d2h=%llu\n", "orient: jpeg", c.ok, c.failed, st.batches, (unsigned long long)st.d2h_bytes);
+                EXPECT(c.bad == 0 && c.ok == (int)st.pictures_ok && c.ok > 0 && st.d2h_bytes == c.bytes && g_orient_calls - orient0 == (int)st.batches);
+            }
+            {   // a device table without the operation: every picture of a call that turns fails with the message; zero turns is not affected
+                g_stub.caps &= ~mvengine::CAP_ORIENT;
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 4;
+                CheckO c; mvhp_decode_stats_t st;
+                const int orient0 = g_orient_calls, recon0 = g_recon_calls + g_geometry_calls + g_jpeg_calls;
+                EXPECT(run_o("orient: table without it", o, s, all, 0, mvhp_output_request_t{MVHP_OUTPUT_ROTATE(2), 0, 0, 0}, c, st) == MVHP_FAILURE);
+                EXPECT(c.bad == 0 && c.ok == 0 && c.no_op == n_idr && g_orient_calls == orient0);
+                EXPECT(g_recon_calls + g_geometry_calls + g_jpeg_calls == recon0);
+                CheckO c0;
+                EXPECT(run_o("orient: table without it, 0", o, s, all, 0, mvhp_output_request_t{MVHP_OUTPUT_ORIENT, 0, 0, 0}, c0, st) == MVHP_SUCCESS && c0.bad == 0 && c0.ok == n_idr);
+                g_stub.caps |= mvengine::CAP_ORIENT;
+            }
+            {   // a malformed request: the box must still be well formed
+                mvhp_engine_opts_t o = base; o.contexts = 1;
+                mvhp_engine_t *e = nullptr;
+                EXPECT(mvhp_engine_create(&o, &e) == MVHP_SUCCESS);
+                const mvhp_output_request_t bad{MVHP_OUTPUT_BOX | MVHP_OUTPUT_ROTATE(1), 1, 40, 0}, unknown{64u, 0, 0, 0};
+                mvhp_decode_stats_t st;
+                EXPECT(mvhp_engine_decode_ex(e, &s3, o3.data(), n3, n3, 0, &bad, nullptr, nullptr, &st) == MVHP_FAILURE);
+                EXPECT(mvhp_engine_decode_ex(e, &s3, o3.data(), n3, n3, 0, &unknown, nullptr, nullptr, &st) == MVHP_FAILURE);
+                mvhp_engine_destroy(e);
+            }
+            {   // minivideo_decode under MINIVIDEO_ROTATE: files of the turned size; malformed values fail before the device is touched
+                char tmpl[] = "/tmp/mvharness_XXXXXX";
+                const char *dir = mkdtemp(tmpl);
+                char cwd[4096];
+                EXPECT(dir != nullptr && getcwd(cwd, sizeof(cwd)) != nullptr);
+                std::string in = argv[4];
+                if (in[0] != '/') in = std::string(cwd) + "/" + in;
+                EXPECT(dir && chdir(dir) == 0);
+                struct Sw { const char *rotate, *thumb; mvhp_output_request_t req; };
+                const Sw sws[] = {{"90", nullptr, mvhp_output_request_t{MVHP_OUTPUT_ROTATE(1), 0, 0, 0}},
+                                  {"270", "40x24", mvhp_output_request_t{MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_ROTATE(3), 40, 24, 0}},
+                                  {"180", nullptr, mvhp_output_request_t{MVHP_OUTPUT_ROTATE(2), 0, 0, 0}},
+                                  {"auto", nullptr, mvhp_output_request_t{}}, {"0", nullptr, mvhp_output_request_t{}}, {"", nullptr, mvhp_output_request_t{}}};
+                for (const Sw &sw : sws)
+                    for (int fmt : {PICTURE_YUV420, PICTURE_BMP}) {
+                        setenv("MINIVIDEO_ROTATE", sw.rotate, 1);
+                        if (sw.thumb) setenv("MINIVIDEO_THUMBNAIL", sw.thumb, 1); else unsetenv("MINIVIDEO_THUMBNAIL");
+                        MediaFile_t *m = nullptr;
+                        EXPECT(minivideo_open(in.c_str(), &m) == SUCCESS);
+                        EXPECT(m && minivideo_parse(m, false, true, false) == SUCCESS);
+                        EXPECT(m && minivideo_decode(m, ".", fmt, 75, n3, PICTURE_UNFILTERED) == SUCCESS);
+                        const int turns = mvhp_output_turns(&s3, &sw.req);
+                        int good = 0, k = 0, expected = 0;
+                        for (int idr = 0; idr < n3; idr++) {
+                            mvhp_output_geometry_t g;
+                            if (mvhp_output_geometry(&s3, idr, &sw.req, &g) != MVHP_SUCCESS) continue;
+                            expected++;
+                            const std::string name = std::string(m->file_name) + "_" + std::to_string(k++) + (fmt == PICTURE_BMP ? ".bmp" : ".yuv");
+                            const std::vector<uint8_t> f = read_file(name);
+                            if (f.empty()) continue;
+                            remove(name.c_str());
+                            const uint64_t h = picture_checksum(s3, idr);
+                            uint64_t got = 0;
+                            if (fmt == PICTURE_YUV420) {
+                                if (f.size() != mvhp_geometry_yuv_bytes(&g)) continue;
+                                memcpy(&got, f.data(), 8);
+                                if (got == h && f.back() == (turns ? kLastYuv : 0x5a)) good++;
+                            } else {
+                                const std::vector<uint8_t> rgb = bmp_pixels(f, (int)g.out_w, (int)g.out_h);
+                                if (rgb.size() != mvhp_geometry_rgb_bytes(&g)) continue;
+                                memcpy(&got, rgb.data() + 8, 8);
+                                if (got == h && rgb.back() == (turns ? kLastRgb : 0xa5)) good++;
+                            }
+                        }
+                        printf("%-28s rotate='%s' thumbnail=%s format=%d files right in %d of %d\n", "public API, orientation", sw.rotate,
+                               sw.thumb ? sw.thumb : "-", fmt, good, expected);
+                        EXPECT(expected >= 4 && good == expected);
+                        EXPECT(minivideo_close(&m) == SUCCESS);
+                    }
+                unsetenv("MINIVIDEO_THUMBNAIL");
+                for (const char *bad : {"45", "90x", "Auto", " 90", "-90", "360"}) {
+                    setenv("MINIVIDEO_ROTATE", bad, 1);
+                    MediaFile_t *m = nullptr;
+                    EXPECT(minivideo_open(in.c_str(), &m) == SUCCESS);
+                    EXPECT(m && minivideo_parse(m, false, true, false) == SUCCESS);
+                    const int ctx_before = g_ctx_created, recon_before = g_recon_calls + g_geometry_calls;
+                    fflush(stdout);
+                    fflush(stderr);
+                    int pipefd[2];
+                    EXPECT(pipe(pipefd) == 0);
+                    const int saved = dup(2);
+                    dup2(pipefd[1], 2);
+                    const int rc = m ? minivideo_decode(m, ".", PICTURE_YUV420, 75, n3, PICTURE_UNFILTERED) : SUCCESS;
+                    fflush(stderr);
+                    dup2(saved, 2);
+                    close(saved);
+                    close(pipefd[1]);
+                    char msg[512] = "";
+                    const ssize_t got = read(pipefd[0], msg, sizeof(msg) - 1);
+                    close(pipefd[0]);
+                    printf("%-28s '%s' rc=%d message: %s", "malformed rotation", bad, rc, got > 0 ? msg : "(none)\n");
+                    EXPECT(rc == FAILURE && got > 0 && strstr(msg, "MINIVIDEO_ROTATE") != nullptr);
+                    EXPECT(g_ctx_created == ctx_before && g_recon_calls + g_geometry_calls == recon_before);
+                    EXPECT(minivideo_close(&m) == SUCCESS);
+                }
+                unsetenv("MINIVIDEO_ROTATE");
+                EXPECT(chdir(cwd) == 0);
+                rmdir(dir);
+            }
+            printf("ORIENT MODE DONE\n");
         }
         if (argc > 5 && !strcmp(argv[5], "score")) {   // ---- score mode: MVHP_OUTPUT_SCORE against the stub's picture-score operation ----
             std::vector<int> order;

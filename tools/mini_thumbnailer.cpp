@@ -1,9 +1,10 @@
 // tools/mini_thumbnailer.cpp -- a small thumbnailer CLI over libminivideo's public API with the
 // same options as the reference's mini_thumbnailer (mini_thumbnailer/src/main.cpp:47-302):
 //   -i <file> [-o <dir>] [-f jpg|png|bmp|tga|yuv420|yuv444] [-q 1..99] [-n 1..999] [-e unfiltered|ordered|distributed]
-// plus two of its own, which set the library's opt-in switches (include/minivideo.h) before the decode call:
+// plus a few of its own, which set the library's opt-in switches (include/minivideo.h) before the decode call:
 //   -c            pictures are the SPS's cropped rectangle (MINIVIDEO_CROP=1)
 //   -s <w>x<h>    ... fitted into a w x h box, never enlarged (MINIVIDEO_THUMBNAIL=<w>x<h>; implies -c)
+//   -r <value>    pictures turned: auto = the MP4's display rotation, or 0 / 90 / 180 / 270 degrees clockwise (MINIVIDEO_ROTATE)
 // The stock mini_thumbnailer also builds unchanged against include/minivideo.h; this file exists so
 // that the GPU box (which has no copy of the reference) has a CLI to run.
 #include <minivideo.h>
@@ -61,6 +62,7 @@ int main(int argc, char *argv[])
             else fprintf(stderr, "-e : No valid extraction mode specified\n");
         } else if (!strcmp(argv[i], "-c")) setenv("MINIVIDEO_CROP", "1", 1);
         else if (!strcmp(argv[i], "-s") && has) setenv("MINIVIDEO_THUMBNAIL", argv[++i], 1);   // (the library checks the value)
+        else if (!strcmp(argv[i], "-r") && has) setenv("MINIVIDEO_ROTATE", argv[++i], 1);      // (the library checks the value)
         else if (!strcmp(argv[i], "-j")) setenv("MINIVIDEO_JPEG", "1", 1);   // -f jpg writes JPEG files (made on the GPU), not the PNG fallback
         else if (!strcmp(argv[i], "-b")) setenv("MINIVIDEO_SKIP_BLANK", "1", 1);   // blank pictures (black, faded, flat) give way to later ones
         else if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) help = true;
@@ -68,7 +70,7 @@ int main(int argc, char *argv[])
     }
     if (!in || help) {
         printf("* Usage:\nmini_thumbnailer -i <filepath> [-o <directory>] [-f picture_format][-q picture_quality]"
-               "[-n picture_number] [-e extraction_mode] [-c] [-s <width>x<height>] [-j] [-b]\n"
+               "[-n picture_number] [-e extraction_mode] [-c] [-s <width>x<height>] [-r auto|0|90|180|270] [-j] [-b]\n"
                "-b : skip blank pictures (MINIVIDEO_SKIP_BLANK=1; MINIVIDEO_BLANK_VARIANCE=<0..16256, default 256>, "
                "MINIVIDEO_BLANK_ALTERNATES=<1..16, default 4>)\n");
         return EXIT_FAILURE;
