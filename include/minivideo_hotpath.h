@@ -221,16 +221,29 @@ MVHP_EXPORT int  mvhp_create(int device, mvhp_ctx_t **out);
 MVHP_EXPORT void mvhp_destroy(mvhp_ctx_t *ctx);
 MVHP_EXPORT const char *mvhp_last_error(void);
 
+/* Alignment, in bytes, of every device buffer handed to the three entry points below: d_packed, d_yuv and d_rgb of
+ * mvhp_recon_batch_dev / mvhp_recon_stages_dev, d_compact and d_packed of mvhp_expand_compact_dev.  The kernels behind them move
+ * records, luma rows and RGB in naturally aligned 16-byte pieces (DESIGN.md 5 "Caller buffers of the reconstruction entry
+ * points" has the widest access per buffer and kernel form).  The per-picture sizes -- 800, 384 and 768 bytes per macroblock --
+ * are multiples of it, so picture k of an aligned buffer is aligned too; a caller that carves its buffers out of a larger
+ * allocation rounds each piece's start up to it.  A pointer below it is refused with MVHP_FAILURE before anything is launched,
+ * and mvhp_last_error() names the argument.  mvhp_recon_align() returns the same number. */
+#define MVHP_RECON_ALIGN 16
+MVHP_EXPORT size_t mvhp_recon_align(void);
+
 /* Reconstruct n_frames pictures whose packed records are resident in device
  * memory.  d_yuv receives n_frames * mvhp_yuv_frame_bytes(); d_rgb (may be
- * NULL) receives n_frames * mvhp_rgb_frame_bytes().  `stream` is a hipStream_t
+ * NULL) receives n_frames * mvhp_rgb_frame_bytes(); d_packed, d_yuv and d_rgb
+ * are MVHP_RECON_ALIGN-byte aligned.  `stream` is a hipStream_t
  * (NULL = the context's own stream).  Asynchronous with respect to the host. */
 MVHP_EXPORT int  mvhp_recon_batch_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p,
                                       const void *d_packed, int n_frames,
                                       uint8_t *d_yuv, uint8_t *d_rgb, void *stream);
 
 /* n_pictures compact pictures (see "Compact pictures" above), `stride` bytes apart in device memory, -> packed records
- * (n_pictures * mvhp_packed_frame_bytes()) in device memory.  Asynchronous on `stream` (NULL = the context's own). */
+ * (n_pictures * mvhp_packed_frame_bytes()) in device memory.  d_compact and d_packed are MVHP_RECON_ALIGN-byte aligned, `stride` is
+ * a multiple of 4 (the kernel reads the compact pictures in 4-byte words; the pointer's rule is the one rule of the three entry
+ * points).  Asynchronous on `stream` (NULL = the context's own). */
 MVHP_EXPORT int  mvhp_expand_compact_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const void *d_compact,
                                          size_t stride, int n_pictures, void *d_packed, void *stream);
 
@@ -240,7 +253,8 @@ MVHP_EXPORT int  mvhp_expand_compact_dev(mvhp_ctx_t *ctx, const mvhp_stream_para
  * bit 2: the deblocking filter alone, in place on d_yuv, with the record headers of d_packed and the params (whatever
  *        p->flags says).
  * Error word of the context (mvhp_sync_check): bit 0 a reconstruction row wait timed out, bit 1 a wide launch's ticket lay
- * outside the launch, bit 2 a deblocking row wait timed out. */
+ * outside the launch, bit 2 a deblocking row wait timed out.
+ * d_packed, d_yuv and d_rgb (may be NULL) are MVHP_RECON_ALIGN-byte aligned, whichever stages run. */
 #define MVHP_STAGE_RECON   1
 #define MVHP_STAGE_COLOR   2
 #define MVHP_STAGE_DEBLOCK 4

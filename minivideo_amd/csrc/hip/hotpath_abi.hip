@@ -348,6 +348,18 @@ static int launch_all(mvhp_ctx *c, const mvhp_stream_params_t *p, const void *d_
     return MVHP_SUCCESS;
 }
 
+MVHP_EXPORT size_t mvhp_recon_align(void) { return MVHP_RECON_ALIGN; }
+
+// The caller buffers of the three reconstruction entry points (MVHP_RECON_ALIGN in minivideo_hotpath.h: the kernels behind them
+// use naturally aligned 16-byte accesses): true when `ptr` (NULL passes: an absent optional buffer) is aligned, else the error
+// text names the argument.  Asked before hipSetDevice and before anything is launched.
+static bool recon_aligned(const char *fn, const char *arg, const void *ptr)
+{
+    if (((uintptr_t)ptr & (uintptr_t)(MVHP_RECON_ALIGN - 1)) == 0) return true;
+    set_err("%s: %s is not %d-byte aligned", fn, arg, MVHP_RECON_ALIGN);
+    return false;
+}
+
 MVHP_EXPORT int mvhp_recon_batch_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p, const void *d_packed,
                                      int n_frames, uint8_t *d_yuv, uint8_t *d_rgb, void *stream)
 {
@@ -355,6 +367,9 @@ MVHP_EXPORT int mvhp_recon_batch_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *
         set_err("mvhp_recon_batch_dev: invalid argument");
         return MVHP_FAILURE;
     }
+    if (!recon_aligned("mvhp_recon_batch_dev", "d_packed", d_packed) || !recon_aligned("mvhp_recon_batch_dev", "d_yuv", d_yuv) ||
+        !recon_aligned("mvhp_recon_batch_dev", "d_rgb", d_rgb))
+        return MVHP_FAILURE;
     HIP_TRY(hipSetDevice(c->device));
     return launch_all(c, p, d_packed, n_frames, d_yuv, d_rgb, stream_of(c, stream), true, true, (p->flags & MVHP_PARAM_DEBLOCK) != 0);
 }
@@ -367,6 +382,8 @@ MVHP_EXPORT int mvhp_expand_compact_dev(mvhp_ctx_t *c, const mvhp_stream_params_
         set_err("mvhp_expand_compact_dev: invalid argument");
         return MVHP_FAILURE;
     }
+    if (!recon_aligned("mvhp_expand_compact_dev", "d_compact", d_compact) || !recon_aligned("mvhp_expand_compact_dev", "d_packed", d_packed))
+        return MVHP_FAILURE;
     HIP_TRY(hipSetDevice(c->device));
     mvhp::ExpandArgs a;
     a.compact = (const uint8_t *)d_compact;
@@ -385,6 +402,9 @@ MVHP_EXPORT int mvhp_recon_stages_dev(mvhp_ctx_t *c, const mvhp_stream_params_t 
         set_err("mvhp_recon_stages_dev: invalid argument");
         return MVHP_FAILURE;
     }
+    if (!recon_aligned("mvhp_recon_stages_dev", "d_packed", d_packed) || !recon_aligned("mvhp_recon_stages_dev", "d_yuv", d_yuv) ||
+        !recon_aligned("mvhp_recon_stages_dev", "d_rgb", d_rgb))
+        return MVHP_FAILURE;
     HIP_TRY(hipSetDevice(c->device));
     const hipStream_t st = stream_of(c, stream);
     const bool recon = (stages & MVHP_STAGE_RECON) != 0;

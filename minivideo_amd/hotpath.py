@@ -10,6 +10,9 @@ PARAM_MAY_HAVE_8X8, PARAM_SPEC_LUMA_DC, PARAM_SLICES, PARAM_SCALING, PARAM_DEBLO
 STAGE_RECON, STAGE_COLOR, STAGE_DEBLOCK = 1, 2, 4                      # mvhp_recon_stages_dev (MVHP_STAGE_*)
 MB_BYTES = 800
 MB_HEADER_BYTES = 32
+# MVHP_RECON_ALIGN (= mvhp_recon_align()): alignment of d_packed / d_yuv / d_rgb of recon_dev and recon_stages_dev and of
+# d_compact / d_packed of expand_compact_dev; a pointer below it is refused before anything is launched
+RECON_ALIGN = 16
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -247,6 +250,8 @@ def lib():
     L.mvhp_set_fused_color.argtypes = [vp, i32]
     L.mvhp_set_crop_copy.restype = i32
     L.mvhp_set_crop_copy.argtypes = [vp, i32]
+    L.mvhp_recon_align.restype = sz
+    L.mvhp_recon_align.argtypes = []
     L.mvhp_recon_batch_dev.restype = i32
     L.mvhp_recon_batch_dev.argtypes = [vp, pp, vp, i32, vp, vp, vp]
     L.mvhp_expand_compact_dev.restype = i32
