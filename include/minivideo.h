@@ -35,6 +35,10 @@
  *     baseline JFIF files coded on the GPU from the 4:2:0 planes as export.c:341-430 does with libjpeg (2x2 / 1x1 / 1x1
  *     sampling, no colour conversion), at picture_quality (clamped to 1 ... 100; otherwise this argument is unused), of the
  *     coded size or of the size MINIVIDEO_CROP / MINIVIDEO_THUMBNAIL ask for.  The other formats are not affected;
+ *   - opt-in, outside the reference's behaviour: with MINIVIDEO_PNG=1 every PNG file (PICTURE_PNG, and PICTURE_JPG without
+ *     MINIVIDEO_JPEG) is a compressed PNG -- row filters and Huffman-only deflate -- coded on the GPU from the picture's RGB
+ *     instead of the stored-deflate file of the host writer: the same names, the same pixels, about half the bytes on camera
+ *     content, and only the files' bytes are downloaded.  It composes with every switch above and below;
  *   - opt-in, outside the reference's behaviour and independent of the switches above: MINIVIDEO_SKIP_BLANK=1 replaces blank
  *     pictures -- black lead-ins, fades, flat title cards -- by later ones.  Every decoded picture gets a score on the GPU,
  *     the variance of its luma samples (of the SPS's cropped rectangle under MINIVIDEO_CROP / MINIVIDEO_THUMBNAIL, else of the

@@ -386,6 +386,51 @@ MVHP_EXPORT int    mvhp_jpeg_encode_dev(mvhp_ctx_t *ctx, const mvhp_output_geome
                                         mvhp_jpeg_entry_t *d_table, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * PNG output (opt-in; DESIGN.md 3 "PNG output"): compressed PNG files made on the device from dense RGB8 pictures.  The format
+ * is fixed, so a file is a function of the samples alone (tests/png_ref.py restates it): signature, IHDR (8 bit, colour type 2,
+ * no interlace), one IDAT per segment of mvhp_png_segment_rows(w) rows, IEND; every row filtered with the type (0 .. 4) whose
+ * bytes have the least sum of min(f, 256 - f), ties to the lowest type; every segment one deflate block that starts on a byte,
+ * Huffman-coded literals only (a dynamic block with a code built from the segment's own histogram), or a stored block where that
+ * would not be shorter -- so no file is longer than mvhp_png_max_bytes(w, h).
+ * ------------------------------------------------------------------------- */
+typedef struct mvhp_png_params {
+    uint32_t reserved;       /* 0.  Measurements only: MVHP_PNG_STAGE_* bits run just those stages of a call made before with the
+                                same arguments (its scratch buffer holds what they need).  The write stage checks every table
+                                entry against cap_bytes again, so a stale table cannot send a store outside the blob          */
+} mvhp_png_params_t;
+#define MVHP_PNG_STAGE_ANALYSE 1u  /* filter types, histograms, code lengths and chunk lengths into the context's scratch buffer */
+#define MVHP_PNG_STAGE_PLACE   2u  /* the scans: writes the table                                                             */
+#define MVHP_PNG_STAGE_WRITE   4u  /* write pass + signature, IHDR, IEND: writes the blob                                      */
+
+#define MVHP_PNG_OK      MVHP_JPEG_OK
+#define MVHP_PNG_TOO_BIG MVHP_JPEG_TOO_BIG   /* the picture did not fit into what was left of the blob: length 0, nothing written */
+typedef mvhp_jpeg_entry_t mvhp_png_entry_t;  /* {offset, length, status}: the table of both encoders                               */
+
+#define MVHP_PNG_HEADER_BYTES 33
+#define MVHP_PNG_MAX_WIDTH 21844             /* 3 w + 1 <= 65535: a filtered row fits one stored block                           */
+/* Bytes of a file before its first IDAT chunk (signature + IHDR). */
+MVHP_EXPORT size_t mvhp_png_header_bytes(void);
+/* Rows per segment: max(1, 32768 / (3 w + 1)); 0 for w < 1.  A host function: needs no device. */
+MVHP_EXPORT int    mvhp_png_segment_rows(int w);
+/* The longest file a w x h picture can give (every segment stored): 51 + 17 segments + h (3 w + 1); 0 for sizes below 1.  A
+ * host function: needs no device. */
+MVHP_EXPORT size_t mvhp_png_max_bytes(int w, int h);
+/* n pictures of g->out_w x g->out_h (d_rgb: n * 3 * out_w * out_h bytes, dense RGB8, 4-byte aligned -- what the fused epilogue
+ * leaves for a geometry of the coded size, or mvhp_resample_dev / mvhp_orient_dev; only out_w / out_h are read) -> n PNG files in
+ * d_blob (16-byte aligned, cap_bytes long) and d_table (n entries, 8-byte aligned), placed by the rule of mvhp_jpeg_encode_dev:
+ * in order, each at the next multiple of 16; a picture whose file would pass cap_bytes is marked MVHP_PNG_TOO_BIG, takes no room,
+ * and those behind it that fit are placed as if it were not there.  No byte at or beyond cap_bytes is written, nor any between a
+ * file's end and the next file's start.  n = 0 does nothing.  Refused before any launch (MVHP_FAILURE): n < 0, odd or zero sizes,
+ * widths above MVHP_PNG_MAX_WIDTH, misaligned pointers; pictures of more than 2^28 samples are refused with MVHP_UNSUPPORTED
+ * (lengths are 32-bit).  Asynchronous on `stream` (NULL = the context's own); filter types, code lengths and chunk lengths live in
+ * a scratch buffer of the context (one byte per row, 304 bytes per segment), so two encodes of one context run one after the
+ * other, whatever their streams.  Nothing is shared between workgroups but that buffer between launches, no kernel waits and
+ * nothing survives the call: safe under stream capture once the scratch buffer has its size. */
+MVHP_EXPORT int    mvhp_png_encode_dev(mvhp_ctx_t *ctx, const mvhp_output_geometry_t *g, const mvhp_png_params_t *params,
+                                       const uint8_t *d_rgb, int n, uint8_t *d_blob, size_t cap_bytes, mvhp_png_entry_t *d_table,
+                                       void *stream);
+
+/* ---------------------------------------------------------------------------
  * Picture scores (opt-in; DESIGN.md 3 "Picture scores"): how much a picture shows, measured on the device as the variance of
  * its luma samples, so that a caller can pass over black lead-ins, fades and flat title cards (minivideo_decode does under
  * MINIVIDEO_SKIP_BLANK=1, include/minivideo.h).  The device sums; the score is integer arithmetic on the host.
@@ -580,6 +625,13 @@ MVHP_EXPORT void mvhp_engine_destroy(mvhp_engine_t *e);
  * entries (16 bytes per picture) and the files' bytes. */
 #define MVHP_OUT_JPEG     4
 #define MVHP_JPEG_REQUEST(quality, restart_mcus) (((uint32_t)(quality) & 0xffu) | (((uint32_t)(restart_mcus) & 0xffffu) << 8))
+/* mvhp_engine_decode_ex only (opt-in; "PNG output" above): neither planes nor RGB are downloaded; every picture's RGB -- the fused
+ * epilogue's where the picture is of the coded size, else what the geometry and orientation passes deliver -- is coded on the
+ * device by mvhp_png_encode_dev, and only the files come back.  The sink gets yuv = NULL, rgb = the picture's PNG file and
+ * g->reserved[0] = its length in bytes.  A batch's blob has room for n x mvhp_png_max_bytes(out_w, out_h) (rounded to 16), so no
+ * picture can be too big.  d2h_bytes counts the table entries (16 bytes per picture) and the files' bytes.  Not together with
+ * MVHP_OUT_JPEG. */
+#define MVHP_OUT_PNG      8
 /* MVHP_OUTPUT_SCORE in mvhp_output_request_t::flags (mvhp_engine_decode_ex only; composes with MVHP_OUTPUT_CROP / _BOX and every
  * output kind above): behind whatever reconstructs the batch (and the deblocking filter, where the stream asks for it)
  * mvhp_luma_stats_dev sums the coded planes over each picture's crop rectangle, the 32-byte records come back with the

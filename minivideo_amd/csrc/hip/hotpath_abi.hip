@@ -15,6 +15,7 @@
 #include "blank_policy.h"
 #include "launch_plan.h"
 #include "minivideo_hotpath.h"
+#include "png_format.h"
 #include "recon_kernels.h"
 
 namespace {
@@ -86,6 +87,11 @@ struct mvhp_ctx {
     size_t       d_jpeg_bytes;
     hipEvent_t   jpeg_done;
     hipStream_t  jpeg_stream;
+    // PNG encoder (png_encode.hip): filter types, code lengths and chunk lengths of one batch, kept like the JPEG encoder's
+    void        *d_png;
+    size_t       d_png_bytes;
+    hipEvent_t   png_done;
+    hipStream_t  png_stream;
 };
 
 static hipStream_t stream_of(const mvhp_ctx *c, void *stream) { return stream ? (hipStream_t)stream : c->stream; }
@@ -168,6 +174,8 @@ MVHP_EXPORT void mvhp_destroy(mvhp_ctx_t *c)
     if (c->d_seam) hipFree(c->d_seam);
     if (c->d_jpeg) hipFree(c->d_jpeg);
     if (c->jpeg_done) hipEventDestroy(c->jpeg_done);
+    if (c->d_png) hipFree(c->d_png);
+    if (c->png_done) hipEventDestroy(c->png_done);
     if (c->wide_done) hipEventDestroy(c->wide_done);
     hipStreamDestroy(c->stream);
     delete c;
@@ -626,6 +634,57 @@ MVHP_EXPORT int mvhp_jpeg_encode_dev(mvhp_ctx_t *c, const mvhp_output_geometry_t
     return MVHP_SUCCESS;
 }
 
+MVHP_EXPORT size_t mvhp_png_header_bytes(void) { return MVHP_PNG_HEADER_BYTES; }
+
+MVHP_EXPORT int mvhp_png_segment_rows(int w) { return mvhp::png_segment_rows(w); }
+
+MVHP_EXPORT size_t mvhp_png_max_bytes(int w, int h) { return mvhp::png_max_bytes(w, h); }
+
+MVHP_EXPORT int mvhp_png_encode_dev(mvhp_ctx_t *c, const mvhp_output_geometry_t *g, const mvhp_png_params_t *pp,
+                                    const uint8_t *d_rgb, int n, uint8_t *d_blob, size_t cap_bytes, mvhp_png_entry_t *d_table,
+                                    void *stream)
+{
+    if (!c || !g || !pp || !d_rgb || ((uintptr_t)d_rgb & 3) || n < 0 || !d_blob || ((uintptr_t)d_blob & 15) || !d_table ||
+        ((uintptr_t)d_table & 7) || (pp->reserved & ~7u)) {
+        set_err("mvhp_png_encode_dev: invalid argument");
+        return MVHP_FAILURE;
+    }
+    if (((g->out_w | g->out_h) & 1u) || g->out_w < 2 || g->out_h < 2 || g->out_w > MVHP_PNG_MAX_WIDTH) {
+        set_err("mvhp_png_encode_dev: pictures of %u x %u cannot be coded (even sides of at least 2, widths up to %d: a filtered "
+                "row has to fit a stored block)", g->out_w, g->out_h, MVHP_PNG_MAX_WIDTH);
+        return MVHP_FAILURE;
+    }
+    if ((uint64_t)g->out_w * g->out_h > ((uint64_t)1 << 28)) {   // lengths are 32-bit: a file is at most 3.01 x its samples
+        set_err("mvhp_png_encode_dev: pictures of %u x %u are too large (at most 2^28 samples)", g->out_w, g->out_h);
+        return MVHP_UNSUPPORTED;
+    }
+    if (n == 0) return MVHP_SUCCESS;
+    mvhp::PngArgs a;
+    a.rgb = d_rgb;
+    a.n = n;
+    a.w = (int)g->out_w;
+    a.h = (int)g->out_h;
+    a.stages = pp->reserved ? (int)pp->reserved : (int)(MVHP_PNG_STAGE_ANALYSE | MVHP_PNG_STAGE_PLACE | MVHP_PNG_STAGE_WRITE);
+    a.blob = d_blob;
+    a.cap = cap_bytes;
+    a.table = d_table;
+    HIP_TRY(hipSetDevice(c->device));
+    const hipStream_t st = stream_of(c, stream);
+    const size_t need = mvhp::png_scratch_bytes(a);
+    if (pp->reserved && c->d_png_bytes < need) {
+        set_err("mvhp_png_encode_dev: single stages need a whole call with the same arguments before them");
+        return MVHP_FAILURE;
+    }
+    if (!c->png_done) HIP_TRY(hipEventCreateWithFlags(&c->png_done, hipEventDisableTiming));
+    if (ensure(&c->d_png, &c->d_png_bytes, need) != MVHP_SUCCESS) return MVHP_FAILURE;   // (hipFree waits for the device)
+    if (c->png_stream && c->png_stream != st) HIP_TRY(hipStreamWaitEvent(st, c->png_done, 0));
+    a.scratch = (uint8_t *)c->d_png;
+    HIP_TRY(mvhp::launch_png_encode(a, st));
+    HIP_TRY(hipEventRecord(c->png_done, st));
+    c->png_stream = st;
+    return MVHP_SUCCESS;
+}
+
 MVHP_EXPORT int mvhp_recon_batch_host(mvhp_ctx_t *c, const mvhp_stream_params_t *p, const void *h_packed,
                                       int n_frames, uint8_t *h_yuv, uint8_t *h_rgb)
 {
@@ -853,9 +912,10 @@ int eng_run_batch(DevCtx *d, const mvengine::BatchJob &j, mvengine::BatchDone &d
     const bool resample = j.out_yuv || j.out_rgb;   // (a pass behind the reconstruction writes them: the resample pass, the turn, or both)
     if (j.turns < 0 || j.turns > 3 || (j.turns == 0 && j.mid_yuv) || (j.turns && !resample)) { err = "reconstruction: invalid orientation"; return MVHP_FAILURE; }
     if (!params_ok(p) || !j.d_compact || !j.d_packed || !j.d_yuv || j.n <= 0) { err = "reconstruction: invalid argument"; return MVHP_FAILURE; }
-    if ((resample || j.jpeg) && !j.geom) { err = "reconstruction: no output geometry"; return MVHP_FAILURE; }
+    if ((resample || j.jpeg || j.png) && !j.geom) { err = "reconstruction: no output geometry"; return MVHP_FAILURE; }
     if (j.jpeg && (!j.blob || !j.table || j.out_rgb)) { err = "reconstruction: invalid JPEG output"; return MVHP_FAILURE; }
-    if (j.geom && !resample && !j.jpeg) { err = "reconstruction: an output geometry without an output buffer"; return MVHP_FAILURE; }
+    if (j.png && (j.jpeg || !j.blob || !j.table || !(resample ? j.out_rgb : j.d_rgb))) { err = "reconstruction: invalid PNG output"; return MVHP_FAILURE; }
+    if (j.geom && !resample && !j.jpeg && !j.png) { err = "reconstruction: an output geometry without an output buffer"; return MVHP_FAILURE; }
     ENG_TRY(hipSetDevice(c->device));
     ENG_TRY(hipEventRecord(d->ev[2], c->stream));
     if (mvhp_expand_compact_dev(c, p, j.d_compact, j.stride, j.n, j.d_packed, c->stream) != MVHP_SUCCESS) { err = mvhp_last_error(); return MVHP_FAILURE; }
@@ -873,6 +933,8 @@ int eng_run_batch(DevCtx *d, const mvengine::BatchJob &j, mvengine::BatchDone &d
     }
     if (rc == MVHP_SUCCESS && j.jpeg)
         rc = mvhp_jpeg_encode_dev(c, j.geom, j.jpeg, resample ? j.out_yuv : j.d_yuv, j.n, j.blob, j.blob_cap, j.table, c->stream);
+    if (rc == MVHP_SUCCESS && j.png)
+        rc = mvhp_png_encode_dev(c, j.geom, j.png, resample ? j.out_rgb : j.d_rgb, j.n, j.blob, j.blob_cap, j.table, c->stream);
     if (rc == MVHP_SUCCESS && j.stats) {
         mvhp_output_geometry_t whole{};   // (no geometry: the rectangle is the coded picture)
         whole.crop_w = whole.out_w = p->width_mbs * 16;
@@ -931,7 +993,7 @@ void eng_placed_free(DevCtx *d, void *arena)
 
 const mvengine::DeviceApi g_hip_api = {
     mvhp_device_count, mvhp_host_alloc, mvhp_host_free, eng_ctx_create, eng_ctx_destroy, eng_dev_alloc, eng_dev_free,
-    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT,
+    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_PNG,
     eng_placed_alloc, eng_placed_free,
 };
 

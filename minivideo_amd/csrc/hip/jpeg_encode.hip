@@ -8,7 +8,7 @@
 //                        per lane, the next block's already on their way) and writes the interval's byte length, stuffing and
 //                        marker included
 //   jpeg_scan_kernel     per picture: exclusive scan of the interval lengths (-> offsets inside the file) and the file's length
-//   jpeg_place_kernel    one workgroup: pictures in order at 16-byte-aligned offsets of the blob, {offset, length, status} each;
+//   blob_place_kernel    (blob_place.h) one workgroup: pictures in order at 16-byte-aligned offsets of the blob, {offset, length, status} each;
 //                        a picture that does not fit gets length 0 and takes no room
 //   jpeg_huff_kernel<1>  write: the same walk again, storing the bytes at the offsets
 //   jpeg_head_kernel     one wavefront per picture: the 625 header bytes and the EOI
@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "blob_place.h"
 #include "minivideo_hotpath.h"
 #include "recon_kernels.h"
 
@@ -318,40 +319,6 @@ __global__ __launch_bounds__(256) void jpeg_scan_kernel(JpegShape g, uint32_t *_
     if (tid == 0) totals[blockIdx.x] = carry;
 }
 
-__global__ __launch_bounds__(256) void jpeg_place_kernel(int n, const uint32_t *__restrict__ totals, unsigned long long cap,
-                                                         mvhp_jpeg_entry_t *__restrict__ table)
-{
-    __shared__ uint32_t s_len[1024];
-    __shared__ unsigned long long s_off[1024];
-    __shared__ unsigned long long s_pos;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_pos = 0;
-    for (int c0 = 0; c0 < n; c0 += 1024) {
-        const int cn = min(1024, n - c0);
-        for (int i = tid; i < cn; i += 256) s_len[i] = totals[c0 + i];
-        __syncthreads();
-        if (tid == 0) {
-            unsigned long long pos = s_pos;
-            for (int i = 0; i < cn; i++) {
-                const uint32_t len = s_len[i];
-                s_off[i] = pos;
-                if (pos + len <= cap) pos = (pos + len + 15ull) & ~15ull;
-                else s_len[i] = 0;   // too big: no room taken
-            }
-            s_pos = pos;
-        }
-        __syncthreads();
-        for (int i = tid; i < cn; i += 256) {
-            mvhp_jpeg_entry_t e;
-            e.offset = s_off[i];
-            e.length = s_len[i];
-            e.status = s_len[i] ? MVHP_JPEG_OK : MVHP_JPEG_TOO_BIG;
-            table[c0 + i] = e;
-        }
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(64) void jpeg_head_kernel(JpegHeader hdr, const mvhp_jpeg_entry_t *__restrict__ table,
                                                        uint8_t *__restrict__ blob, unsigned long long cap)
 {
@@ -453,7 +420,7 @@ hipError_t launch_jpeg_encode(const JpegArgs &a, hipStream_t stream)
     if (a.stages & MVHP_JPEG_STAGE_COUNT) {
         jpeg_huff_kernel<false><<<dim3(huff_grid), dim3(64), 0, stream>>>(g, codes, coefs, maps, lens, nullptr, nullptr, 0);
         jpeg_scan_kernel<<<dim3((unsigned)a.n), dim3(256), 0, stream>>>(g, lens, totals);
-        jpeg_place_kernel<<<dim3(1), dim3(256), 0, stream>>>(a.n, totals, (unsigned long long)a.cap, a.table);
+        blob_place_kernel<<<dim3(1), dim3(256), 0, stream>>>(a.n, totals, (unsigned long long)a.cap, a.table);
     }
     if (a.stages & MVHP_JPEG_STAGE_WRITE) {
         JpegHeader hdr;

@@ -139,6 +139,21 @@ hipError_t launch_jpeg_encode(const JpegArgs &a, hipStream_t stream);
 void       jpeg_quant_tables(int quality, uint8_t out[128]);
 void       jpeg_header(int w, int h, int quality, int restart, uint8_t out[MVHP_JPEG_HEADER_BYTES]);
 
+// PNG files from dense RGB8 pictures (png_encode.hip): filter choice + histogram + code lengths, scans, write, headers
+struct PngArgs {
+    const uint8_t     *rgb;      // n pictures of w x h, RGB8, dense, 4-byte aligned
+    int                n, w, h;  // w, h even; 3 w + 1 <= 65535
+    int                stages;   // MVHP_PNG_STAGE_*
+    uint8_t           *blob;     // 16-byte aligned
+    size_t             cap;
+    mvhp_png_entry_t  *table;    // n entries
+    uint8_t           *scratch;  // png_scratch_bytes(), 16-byte aligned
+};
+size_t     png_scratch_bytes(const PngArgs &a);
+hipError_t launch_png_encode(const PngArgs &a, hipStream_t stream);
+void       png_header(int w, int h, uint8_t out[MVHP_PNG_HEADER_BYTES]);
+// (png_segment_rows() and png_max_bytes(): csrc/host/png_format.h, host arithmetic the decode engine shares)
+
 // picture scores (luma_stats.hip): sum and sum of squares of the luma samples of one rectangle of every picture
 struct LumaStatsArgs {
     const uint8_t     *src;          // n coded pictures, 16-byte aligned

@@ -322,10 +322,13 @@ struct ExportSink {
     struct Slot { int idr; uint32_t score; std::string name; };
     std::vector<Slot> *slots = nullptr;
 
-    // file_bytes: PICTURE_JPG under MINIVIDEO_JPEG=1 only -- `rgb` then is the finished file (made on the device)
+    bool png_dev = false;           // MINIVIDEO_PNG=1 and fmt == PICTURE_PNG: the files are made on the device (MVHP_OUT_PNG)
+    bool device_file() const { return fmt == PICTURE_JPG || png_dev; }
+    // file_bytes: PICTURE_JPG under MINIVIDEO_JPEG=1 and PICTURE_PNG under MINIVIDEO_PNG=1 only -- `rgb` then is the finished
+    // file (made on the device)
     int write_one(const std::string &name, int W, int H, const uint8_t *yuv, const uint8_t *rgb, size_t file_bytes) const
     {
-        if (fmt == PICTURE_JPG) {
+        if (device_file()) {
             FILE *f = fopen(name.c_str(), "wb");
             if (!f) return 0;
             const bool ok = fwrite(rgb, 1, file_bytes, f) == file_bytes;
@@ -393,7 +396,7 @@ struct ExportSink {
         name += ".";
         name += x.ext;
         const int W = (int)g->out_w, H = (int)g->out_h;   // the coded size unless MINIVIDEO_CROP / MINIVIDEO_THUMBNAIL ask for less
-        const size_t file_bytes = x.fmt == PICTURE_JPG ? g->reserved[0] : 0;   // (MVHP_OUT_JPEG: the length of the file in `rgb`)
+        const size_t file_bytes = x.device_file() ? g->reserved[0] : 0;   // (MVHP_OUT_JPEG / _PNG: the length of the file in `rgb`)
         if (!x.pool.empty()) {
             if (x.write_errors.load() == 0 && x.slots) x.slots->push_back(Slot{idr, g->reserved[1], name});
             // Writers run behind the pipeline, so a write that fails is only known later: no further picture is decoded in
@@ -451,7 +454,7 @@ struct AlternateSink {
         sc.push_back(g->reserved[1]);
         if (mvblank::choose(sc.data(), (int)sc.size(), a.min_score) != (int)sc.size() - 1) return 1;
         ExportSink::Slot &slot = (*a.slots)[(size_t)k];
-        const size_t file_bytes = x.fmt == PICTURE_JPG ? g->reserved[0] : 0;
+        const size_t file_bytes = x.device_file() ? g->reserved[0] : 0;
         // beside the slot's file first, then renamed over it: a write that fails leaves the file of the earlier candidate whole,
         // which is what `written` counted.  The candidate is then taken out of the slot's scores again, so that a later
         // alternate is weighed against what the file holds.
@@ -657,6 +660,9 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     else if (fmt == PICTURE_BMP) ext = "bmp";
     else if (fmt == PICTURE_TGA) ext = "tga";
     const bool want_rgb = (fmt == PICTURE_PNG || fmt == PICTURE_BMP || fmt == PICTURE_TGA);
+    // opt-in (MINIVIDEO_PNG=1, outside the parity contract): whenever the format resolves to PNG the files are compressed PNG made on
+    // the device from the RGB (DESIGN.md 3 "PNG output") instead of the host writer's stored ones; only their bytes come back
+    const bool png_dev = fmt == PICTURE_PNG && getenv("MINIVIDEO_PNG") && atoi(getenv("MINIVIDEO_PNG")) != 0;
 
     const double t_indexed = wall_s();
     es.join();
@@ -668,15 +674,16 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     sink.fmt = fmt;
     sink.ext = ext;
     sink.want_rgb = want_rgb;
+    sink.png_dev = png_dev;
     sink.picture_number = picture_number;
     {   // file writers: two per sixteen cores keep up with the pipeline on the raw formats (0.5 ms of copying per picture);
         // the entropy threads need the rest.  PNG and TGA cost more CPU per picture than entropy decoding does (two checksums
         // over 6.3 MB, 7 ms; the run-length coder, 5 ms; against 3.7 ms): half as many writers as cores -- they sleep when
         // there is nothing to write, and the scheduler shares the cores between the two kinds of work.
         const int cores = mvengine::effective_cores();
-        int writers = (fmt == PICTURE_PNG || fmt == PICTURE_TGA) ? std::min(16, std::max(2, cores / 2))
+        int writers = ((fmt == PICTURE_PNG && !png_dev) || fmt == PICTURE_TGA) ? std::min(16, std::max(2, cores / 2))
                       : (fmt == PICTURE_BMP)                         ? std::min(8, std::max(2, cores / 4))   // (4 ms: the B-G-R swap)
-                                                                     : std::min(4, std::max(1, cores / 8));
+                                                                     : std::min(4, std::max(1, cores / 8));   // (finished files too)
         if (const char *e = getenv("MINIVIDEO_WRITERS")) writers = std::max(0, std::min(16, atoi(e)));
         if (wanted < 4) writers = 0;
         if (writers > 0) sink.start(writers, eng);
@@ -689,9 +696,9 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     // opt-in (MINIVIDEO_SKIP_BLANK=1, outside the parity contract): the same call with every picture's score, pass 1 of 2
     std::vector<ExportSink::Slot> slots;
     if (blank.on) { req.flags |= MVHP_OUTPUT_SCORE; sink.slots = &slots; }
-    const int out_kind = jpeg ? MVHP_OUT_JPEG : want_rgb ? MVHP_OUT_RGB_ONLY : 0;
+    const int out_kind = jpeg ? MVHP_OUT_JPEG : png_dev ? MVHP_OUT_PNG : want_rgb ? MVHP_OUT_RGB_ONLY : 0;
     (void)mvhp_engine_decode_ex(eng, &s, order.data(), (int)order.size(), wanted, out_kind,
-                                (req.flags || jpeg) ? &req : nullptr, ExportSink::call, &sink, &st);
+                                (req.flags || jpeg) ? &req : nullptr, ExportSink::call, &sink, &st);   // (MVHP_OUT_PNG has no parameters)
     sink.finish();   // (every kept picture is back: mvhp_engine_decode waits for that)
     if (blank.on && !sink.aborted && sink.write_errors.load() == 0) {
         // pass 2: the alternates of every slot whose picture scores below the threshold -- the IDRs between it and the next

@@ -31,6 +31,7 @@
 
 #include "blank_policy.h"
 #include "h264_frontend.h"
+#include "png_format.h"
 #include "stream_internal.h"
 
 namespace mvengine {
@@ -113,7 +114,7 @@ struct InChunk {
 };
 
 struct OutChunk {
-    Pinned yuv, rgb;         // (MVHP_OUT_JPEG: rgb holds the files of the chunk's pictures, tab their table entries)
+    Pinned yuv, rgb;         // (MVHP_OUT_JPEG, MVHP_OUT_PNG: rgb holds the files of the chunk's pictures, tab their table entries)
     Pinned tab;
     Pinned stats;            // (MVHP_OUTPUT_SCORE: the records of the chunk's pictures)
     int refs = 0;            // pictures handed to the sink queue and not yet consumed
@@ -142,7 +143,7 @@ enum BufKind {
     kOutYuv,     // output pictures of a batch with a geometry (what is downloaded then)
     kOutRgb,
     kMidYuv,     // a batch that scales AND turns: the resampled planes before the turn (the turn reads them, nothing downloads them)
-    kJpegBlob,   // MVHP_OUT_JPEG: the encoder's blob (n x the raw picture) ...
+    kJpegBlob,   // MVHP_OUT_JPEG: the encoder's blob (n x the raw picture); MVHP_OUT_PNG: n x the longest file ...
     kJpegTab,    // ... and table of a batch
     kStats,      // MVHP_OUTPUT_SCORE: the records of a batch (n x 32 bytes)
     kBufKinds,
@@ -179,6 +180,7 @@ size_t write_empty_compact(uint8_t *buf, size_t mbs)
 struct Wants {
     bool yuv = true, rgb = false;   // which of them are downloaded (the planes are always reconstructed)
     bool jpeg = false;              // MVHP_OUT_JPEG: neither of them; JPEG files made on the device
+    bool png = false;               // MVHP_OUT_PNG: neither of them; PNG files made on the device from the RGB
     bool score = false;             // MVHP_OUTPUT_SCORE (it changes no picture and no path)
     int turns = 0;                  // quarter turns the request applies (mvhp_output_turns): one value per call
 };
@@ -189,7 +191,14 @@ bool scales_before_turn(const mvhp_output_geometry_t &g, int turns)
     return turns != 0 && (w != g.crop_w || h != g.crop_h);
 }
 // what a placed arena and the job's largest batch are planned for: pictures of the coded size, planes and RGB
-constexpr Wants kPlanesAndRgb = {true, true, false, false, 0};
+constexpr Wants kPlanesAndRgb = {true, true, false, false, false, 0};
+
+// MVHP_OUT_PNG: the room of one picture in the blob -- the longest file there is (every segment stored), so that no picture can be
+// too big, rounded to the 16 bytes files are placed at
+size_t png_blob_bytes(const mvhp_output_geometry_t &g)
+{
+    return (mvhp::png_max_bytes((int)g.out_w, (int)g.out_h) + 15) & ~(size_t)15;
+}
 
 // Device bytes per picture of one kind, for a batch of these parameters and this geometry (use_geom: it differs from the coded
 // size) in a call with these outputs; 0 = such a batch has no buffer of the kind.  The only place where the size of a batch
@@ -200,12 +209,12 @@ size_t picture_bytes(BufKind k, const mvhp_stream_params_t &p, const mvhp_output
     case kCompact:  return compact_slot_bytes(p);
     case kPacked:   return mvhp_packed_frame_bytes(&p);
     case kYuv:      return mvhp_yuv_frame_bytes(&p);
-    case kRgb:      return w.rgb && !use_geom ? mvhp_rgb_frame_bytes(&p) : 0;
+    case kRgb:      return (w.rgb || w.png) && !use_geom ? mvhp_rgb_frame_bytes(&p) : 0;
     case kOutYuv:   return use_geom && (w.yuv || w.jpeg) ? mvhp_geometry_yuv_bytes(&g) : 0;
-    case kOutRgb:   return use_geom && w.rgb ? mvhp_geometry_rgb_bytes(&g) : 0;
+    case kOutRgb:   return use_geom && (w.rgb || w.png) ? mvhp_geometry_rgb_bytes(&g) : 0;
     case kMidYuv:   return use_geom && scales_before_turn(g, w.turns) ? mvhp_geometry_yuv_bytes(&g) : 0;
-    case kJpegBlob: return w.jpeg ? mvhp_geometry_yuv_bytes(&g) : 0;
-    case kJpegTab:  return w.jpeg ? sizeof(mvhp_jpeg_entry_t) : 0;
+    case kJpegBlob: return w.jpeg ? mvhp_geometry_yuv_bytes(&g) : w.png ? png_blob_bytes(g) : 0;
+    case kJpegTab:  return w.jpeg || w.png ? sizeof(mvhp_jpeg_entry_t) : 0;
     case kStats:    return w.score ? sizeof(mvhp_luma_stats_t) : 0;
     default:        return 0;
     }
@@ -219,6 +228,11 @@ size_t batch_picture_bytes(const mvhp_stream_params_t &p, const mvhp_output_geom
     size_t sum = 0;
     for (int k = 0; k < kBufKinds; k++) sum += picture_bytes((BufKind)k, p, g, use_geom, w);
     if (w.jpeg) sum += mvhp_geometry_yuv_bytes(&g) * 17 / 4 - mvhp_geometry_yuv_bytes(&g) - sizeof(mvhp_jpeg_entry_t);
+    // (the PNG encoder's scratch: one byte per row, 304 per segment -- and a segment has at least one row)
+    if (w.png && g.out_w) {
+        const size_t R = (size_t)mvhp::png_segment_rows((int)g.out_w);
+        sum += (size_t)g.out_h + 304 * (((size_t)g.out_h + R - 1) / R) + 16;
+    }
     return sum;
 }
 
@@ -331,6 +345,7 @@ private:
     int n_order_ = 0, wanted_ = 0;
     Wants w_;                                   // (score: taken out of req_.flags)
     mvhp_jpeg_params_t jpeg_{};
+    mvhp_png_params_t png_{};
     mvhp_output_request_t req_{};               // flags 0: pictures of the coded size
     bool stop_ = false;
     bool sink_waiting_ = false;
@@ -958,6 +973,7 @@ void Engine::launcher(int k)
         if (inject) err = "injected failure (test hook)";
         else if (w_.score && !(api_.caps & CAP_SCORE)) err = "this device table has no picture-score operation";
         else if (w_.jpeg && !(api_.caps & CAP_JPEG)) err = "this device table has no JPEG operation";
+        else if (w_.png && !(api_.caps & CAP_PNG)) err = "this device table has no PNG operation";
         else if (b->use_geom && !w_.jpeg && !(api_.caps & CAP_GEOMETRY)) err = "this device table has no output-geometry operation";
         else if (w_.turns && !(api_.caps & CAP_ORIENT)) err = "this device table has no orientation operation";
         else {
@@ -970,12 +986,13 @@ void Engine::launcher(int k)
             job.n = b->total;
             job.d_yuv = buf(kYuv);
             job.d_rgb = buf(kRgb);
-            job.geom = b->use_geom || w_.jpeg ? &b->geom : nullptr;
+            job.geom = b->use_geom || w_.jpeg || w_.png ? &b->geom : nullptr;
             job.out_yuv = buf(kOutYuv);
             job.out_rgb = buf(kOutRgb);
             job.turns = w_.turns;
             job.mid_yuv = buf(kMidYuv);
             job.jpeg = w_.jpeg ? &jpeg_ : nullptr;
+            job.png = w_.png ? &png_ : nullptr;
             job.blob = buf(kJpegBlob);
             job.blob_cap = (size_t)b->total * need(*b, kJpegBlob);
             job.table = (mvhp_jpeg_entry_t *)buf(kJpegTab);
@@ -1076,7 +1093,7 @@ void Engine::downloader(int k)
                 continue;
             }
             if (sb) recs = (const mvhp_luma_stats_t *)oc->stats.p;
-            if (w_.jpeg) {   // the table rows of the chunk's pictures, then exactly the bytes they name, one piece per file
+            if (w_.jpeg || w_.png) {   // the table rows of the chunk's pictures, then exactly the bytes they name, one piece per file
                 const mvhp_jpeg_entry_t *tab = nullptr;
                 const size_t tb = need(*b, kJpegTab);
                 size_t base = 0, span = 0, moved = (size_t)n * tb;
@@ -1096,7 +1113,7 @@ void Engine::downloader(int k)
                         if (tab[i].status != MVHP_JPEG_OK) continue;
                         if (tab[i].offset < base || tab[i].offset > blob_cap || tab[i].length > blob_cap - tab[i].offset) {
                             ok = false;
-                            err = "the JPEG table names bytes outside the blob";
+                            err = w_.png ? "the PNG table names bytes outside the blob" : "the JPEG table names bytes outside the blob";
                         }
                         span = std::max(span, (size_t)(tab[i].offset - base) + tab[i].length);
                     }
@@ -1132,7 +1149,7 @@ void Engine::downloader(int k)
                                 oc->refs++;
                             } else {   // a JPEG larger than the raw picture is of no use: the picture fails, decoding goes on
                                 r.rc = MVHP_FAILURE;
-                                r.err = "the JPEG file does not fit into the room of the raw picture";
+                                r.err = w_.png ? "the PNG file does not fit into the blob" : "the JPEG file does not fit into the room of the raw picture";
                             }
                             if (recs) r.geom.reserved[1] = mvblank::luma_score(recs[i].sum, recs[i].sumsq, recs[i].samples);
                             r.yuv = nullptr;
@@ -1212,6 +1229,11 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         err = "MVHP_OUT_JPEG needs mvhp_engine_decode_ex: its sink gets the file's length with the geometry";
         return MVHP_FAILURE;
     }
+    if ((out_mask & MVHP_OUT_PNG) && (sink || (out_mask & MVHP_OUT_JPEG))) {
+        err = sink ? "MVHP_OUT_PNG needs mvhp_engine_decode_ex: its sink gets the file's length with the geometry"
+                   : "MVHP_OUT_PNG and MVHP_OUT_JPEG are two output kinds: a call delivers one";
+        return MVHP_FAILURE;
+    }
     if (!order || n_order <= 0 || wanted <= 0) { err = "nothing to decode"; return MVHP_FAILURE; }
     for (int i = 0; i < n_order; i++)
         if (order[i] < 0 || (size_t)order[i] >= s.idrs.size()) { err = "IDR index out of range"; return MVHP_FAILURE; }
@@ -1221,8 +1243,9 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         std::lock_guard<std::mutex> l(mu_);
         s_ = &s; order_ = order; n_order_ = n_order; wanted_ = std::min(wanted, n_order);
         w_.jpeg = (out_mask & MVHP_OUT_JPEG) != 0;
-        w_.rgb = !w_.jpeg && (out_mask & 1) != 0;
-        w_.yuv = !w_.jpeg && (!w_.rgb || (out_mask & 2) == 0);
+        w_.png = (out_mask & MVHP_OUT_PNG) != 0;
+        w_.rgb = !w_.jpeg && !w_.png && (out_mask & 1) != 0;
+        w_.yuv = !w_.jpeg && !w_.png && (!w_.rgb || (out_mask & 2) == 0);
         jpeg_ = mvhp_jpeg_params_t{};
         if (w_.jpeg) {   // mvhp_output_request_t::reserved carries the encoder's parameters
             const uint32_t rsv = req ? req->reserved : 0;

@@ -30,7 +30,7 @@ struct BatchJob {
     uint8_t *d_yuv;   // n x planes of the coded size: always written (after the deblocking filter where params ask for it).  The
                       // output of a job with nothing below, the scratch every later pass reads otherwise
     uint8_t *d_rgb;   // fused RGB of the coded size, or NULL.  Only without a resample pass and without JPEG: those reconstruct
-                      // planes only, without the fused colour epilogue
+                      // planes only, without the fused colour epilogue (with `png` and no pass in between it is the encoder's input)
     const mvhp_output_geometry_t *geom;   // of the n pictures; NULL: the coded size, nothing below but `stats` may be set
     uint8_t *out_yuv, *out_rgb;   // (turns 0) mvhp_resample_dev of d_yuv into n pictures of `geom`: planes and / or RGB (either may be NULL);
                                   // both NULL: no resample pass (only with `jpeg`: files of the coded size, geom names that size)
@@ -40,6 +40,9 @@ struct BatchJob {
                         // geometry before the turn) and mvhp_orient_dev of those
     const mvhp_jpeg_params_t *jpeg;   // NULL: no encoder.  Else mvhp_jpeg_encode_dev of the n pictures of `geom` -- out_yuv where a
                                       // resample pass ran, else d_yuv -- into `blob` (blob_cap bytes) and `table` (n entries)
+    const mvhp_png_params_t *png;     // NULL: no PNG encoder (never beside `jpeg`).  Else mvhp_png_encode_dev of the n pictures of
+                                      // `geom` -- out_rgb where a pass behind the reconstruction wrote it, else the fused d_rgb --
+                                      // into the same `blob` and `table`
     uint8_t *blob; size_t blob_cap; mvhp_jpeg_entry_t *table;
     mvhp_luma_stats_t *stats;   // NULL: no picture scores.  Else mvhp_luma_stats_dev over the crop rectangle of `geom` (the whole
                                 // picture without one) on the n coded planes in d_yuv -> n records
@@ -50,7 +53,7 @@ struct BatchDone {
 };
 
 // what run_batch can do beyond pictures of the coded size; a job that needs a missing bit fails in the engine, with a message
-enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4, CAP_ORIENT = 8 };
+enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4, CAP_ORIENT = 8, CAP_PNG = 16 };
 
 // Every operation blocks its calling thread until the device has finished it; the engine runs one thread per queue
 // and context, which is what overlaps upload(k+1), kernel(k) and download(k-1).  *ms = device-side duration.

@@ -55,6 +55,7 @@ class StreamParams(C.Structure):
 
 
 OUT_JPEG = 4                                                            # mvhp_engine_decode_ex output kind (MVHP_OUT_JPEG)
+OUT_PNG = 8                                                             # ... (MVHP_OUT_PNG)
 OUTPUT_CROP, OUTPUT_BOX, OUTPUT_SCORE = 1, 2, 4                          # mvhp_output_request_t flags (MVHP_OUTPUT_*)
 OUTPUT_ORIENT, OUTPUT_ROTATE_SHIFT = 8, 4                                # ... the stream's own rotation; bits 4-5: further turns
 ORIENT_SRC_CODED = 1                                                    # mvhp_orient_dev src_flags (MVHP_ORIENT_SRC_CODED)
@@ -135,6 +136,31 @@ def jpeg_quant_tables(quality):
     if lib().mvhp_jpeg_quant_tables(int(quality), out.ctypes.data) != SUCCESS:
         raise MiniVideoError("mvhp_jpeg_quant_tables failed")
     return out.reshape(2, 64)
+
+
+class PngParams(C.Structure):
+    """mvhp_png_params_t"""
+    _fields_ = [("reserved", C.c_uint32)]
+
+
+PNG_OK, PNG_TOO_BIG = 0, 1                                              # mvhp_png_entry_t status (MVHP_PNG_*)
+PNG_STAGE_ANALYSE, PNG_STAGE_PLACE, PNG_STAGE_WRITE = 1, 2, 4           # measurements only (MVHP_PNG_STAGE_*)
+PNG_ENTRY_DTYPE = JPEG_ENTRY_DTYPE                                      # mvhp_png_entry_t: the table of both encoders
+PNG_MAX_WIDTH = 21844                                                   # MVHP_PNG_MAX_WIDTH
+
+
+def png_header_bytes():
+    return int(lib().mvhp_png_header_bytes())
+
+
+def png_segment_rows(w):
+    """mvhp_png_segment_rows: rows per segment (= per IDAT chunk) of pictures w wide (no device needed)"""
+    return int(lib().mvhp_png_segment_rows(int(w)))
+
+
+def png_max_bytes(w, h):
+    """mvhp_png_max_bytes: the longest file a w x h picture can give (no device needed)"""
+    return int(lib().mvhp_png_max_bytes(int(w), int(h)))
 
 
 class LumaStats(C.Structure):
@@ -302,6 +328,14 @@ def lib():
     L.mvhp_jpeg_quant_tables.argtypes = [i32, vp]
     L.mvhp_jpeg_encode_dev.restype = i32
     L.mvhp_jpeg_encode_dev.argtypes = [vp, pg, C.POINTER(JpegParams), vp, i32, vp, sz, vp, vp]
+    L.mvhp_png_header_bytes.restype = sz
+    L.mvhp_png_header_bytes.argtypes = []
+    L.mvhp_png_segment_rows.restype = i32
+    L.mvhp_png_segment_rows.argtypes = [i32]
+    L.mvhp_png_max_bytes.restype = sz
+    L.mvhp_png_max_bytes.argtypes = [i32, i32]
+    L.mvhp_png_encode_dev.restype = i32
+    L.mvhp_png_encode_dev.argtypes = [vp, pg, C.POINTER(PngParams), vp, i32, vp, sz, vp, vp]
     L.mvhp_stream_last_error.restype = C.c_char_p
     if hasattr(L, "mvhp_stream_open"):
         L.mvhp_stream_open.restype = i32
@@ -425,6 +459,15 @@ class HotPath:
         """test-only: luma rows per workgroup of luma_stats_dev, 0 = choose (speed only: the records do not depend on it)"""
         if self._L.mvhp_set_stats_band(self._h, int(rows)) != SUCCESS:
             raise MiniVideoError("mvhp_set_stats_band(%d) failed" % rows)
+
+    def png_encode_dev(self, geom, d_rgb, n, d_blob, cap_bytes, d_table, stream=None, stages=0):
+        """n pictures of OutputGeometry `geom` (dense RGB8, device) -> PNG files in d_blob (16-byte aligned, cap_bytes) and n
+        records (PNG_ENTRY_DTYPE) in d_table, both device memory.  Asynchronous.  stages: measurements only (PNG_STAGE_*), 0 = the
+        whole encode."""
+        pp = PngParams(int(stages))
+        rc = self._L.mvhp_png_encode_dev(self._h, C.byref(geom), C.byref(pp), d_rgb, int(n), d_blob, int(cap_bytes), d_table, stream)
+        if rc != SUCCESS:
+            raise _err(self._L, "mvhp_png_encode_dev")
 
     def jpeg_encode_dev(self, geom, d_yuv, n, d_blob, cap_bytes, d_table, quality=75, restart_mcus=0, stream=None, stages=0):
         """n pictures of OutputGeometry `geom` (planar, device) -> JPEG files in d_blob (16-byte aligned, cap_bytes) and n
@@ -585,7 +628,7 @@ class Engine:
         self._L.mvhp_engine_release_picture(self._h, int(seq))
 
     def decode(self, stream_handle, order, wanted=None, want_rgb=False, sink=None, output=None, jpeg=None, restart_mcus=0,
-               score=False, rotate=None):
+               score=False, rotate=None, png=False):
         """sink(seq, idr, rc, err, params, yuv ndarray | None, rgb ndarray | None) -> 1 accept / 0 reject / -1 stop /
         2 accept and keep until release_picture(seq); the arrays are views of page-locked memory valid only during the call
         (or until the release).  Returns (rc, stats dict).
@@ -595,6 +638,8 @@ class Engine:
         jpeg = a quality (1 .. 100): MVHP_OUT_JPEG -- the pictures (of the coded size, or of `output`) are coded as JPEG on the
         device and only the files come back: sink(seq, idr, rc, err, params, geometry, None, file bytes as a uint8 array);
         want_rgb is ignored; restart_mcus 0 = one MCU row.
+        png=True: MVHP_OUT_PNG -- the pictures' RGB is coded as PNG on the device and only the files come back, handed to the sink
+        as the JPEG files are; not together with jpeg.
         score=True: MVHP_OUTPUT_SCORE -- the sink is called as for `output` (with the geometry, also for pictures of the coded
         size) and finds each picture's score in geometry.score; the pictures are the same bytes.
         rotate = "auto" (the stream's own rotation, stream_rotation()) or 0 / 90 / 180 / 270 (clockwise): the pictures are
@@ -602,7 +647,9 @@ class Engine:
         order = (C.c_int * len(order))(*order)
         st = DecodeStats()
         n_wanted = len(order) if wanted is None else wanted
-        if output is not None or jpeg is not None or score or rotate is not None:
+        if png and jpeg is not None:
+            raise ValueError("png and jpeg are two output kinds: a call delivers one")
+        if output is not None or jpeg is not None or score or rotate is not None or png:
             req = output_request(output, rotate) or OutputRequest(0, 0, 0, 0)
             if score:
                 req.flags |= OUTPUT_SCORE
@@ -614,12 +661,12 @@ class Engine:
                     return 1 if rc == SUCCESS else 0
                 pr, geom = p.contents, OutputGeometry.from_buffer_copy(g.contents)
                 y = np.ctypeslib.as_array(yuv, shape=(geom.yuv_bytes,)) if yuv else None
-                r = np.ctypeslib.as_array(rgb, shape=(geom.reserved[0] if jpeg is not None else geom.rgb_bytes,)) if rgb else None
+                r = np.ctypeslib.as_array(rgb, shape=(geom.reserved[0] if jpeg is not None or png else geom.rgb_bytes,)) if rgb else None
                 return int(sink(seq, idr, rc, err.decode() if err else "", pr, geom, y, r))
 
             cbx = SINK_EX_T(_cbx) if sink is not None else C.cast(None, SINK_EX_T)
             rc = self._L.mvhp_engine_decode_ex(self._h, stream_handle, order, len(order), n_wanted,
-                                               OUT_JPEG if jpeg is not None else int(want_rgb), C.byref(req), cbx, None, C.byref(st))
+                                               OUT_JPEG if jpeg is not None else OUT_PNG if png else int(want_rgb), C.byref(req), cbx, None, C.byref(st))
             return rc, st.as_dict()
 
         def _cb(user, seq, idr, rc, err, p, yuv, rgb):

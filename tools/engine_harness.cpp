@@ -4,9 +4,9 @@
 // lets the sink check that the right picture arrives in the right place, in order, through chunks, batches, several
 // contexts and a re-queue.  Nothing here is part of libminivideo.so.
 //
-// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes> [jpeg | score | orient]]]
+// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes> [jpeg | png | score | orient]]]
 // The fourth argument adds the geometry mode: mvhp_engine_decode_ex and minivideo_decode under MINIVIDEO_CROP /
-// MINIVIDEO_THUMBNAIL against the stub's resample targets.  A fifth argument adds the JPEG mode (MVHP_OUT_JPEG) or the
+// MINIVIDEO_THUMBNAIL against the stub's resample targets.  A fifth argument adds the JPEG mode (MVHP_OUT_JPEG), the PNG mode (MVHP_OUT_PNG against the stub's PNG operation) or the
 // score mode (MVHP_OUTPUT_SCORE against the stub's picture scores, which sum the stub's coded planes on the CPU), or the orient
 // mode (MVHP_OUTPUT_ORIENT / MVHP_OUTPUT_ROTATE and MINIVIDEO_ROTATE against the stub's turn).
 #include <stdio.h>
@@ -26,6 +26,7 @@
 
 #include "blank_policy.h"
 #include "decode_engine.h"
+#include "png_format.h"
 #include "minivideo.h"
 #include "stream_internal.h"
 
@@ -137,8 +138,14 @@ mvhp_luma_stats_t expected_stats(uint64_t h, bool pattern, const mvhp_stream_par
 //   must hold n pictures of it -- and a batch that scales before the turn must bring the buffer of the unturned planes, which is
 //   written in full, and no other batch may bring one;
 // * scores: honest sums over the rectangle of the coded planes the batch buffer holds.
-constexpr uint8_t kLastYuv = 0x77, kLastRgb = 0x78, kLastJpeg = 0x79;
-std::atomic<int> g_jpeg_calls{0}, g_stats_calls{0}, g_orient_calls{0}, g_mid_calls{0};
+// * PNG: the RGB the encoder reads is stamped as above (the fused RGB of a batch of the coded size, the resample or turn target
+//   otherwise; no output planes), and every picture gets a "file" of 64 + checksum % (the longest file - 64) bytes of 0x3d that
+//   starts with bytes 8-15 of that RGB (the checksum) and ends in 0x7a; the blob must be n x the longest file rounded to 16, so
+//   no picture is too big.
+constexpr uint8_t kLastYuv = 0x77, kLastRgb = 0x78, kLastJpeg = 0x79, kLastPng = 0x7a;
+std::atomic<int> g_jpeg_calls{0}, g_stats_calls{0}, g_orient_calls{0}, g_mid_calls{0}, g_png_calls{0};
+size_t stub_png_room(const mvhp_output_geometry_t *g) { return (mvhp::png_max_bytes((int)g->out_w, (int)g->out_h) + 15) & ~(size_t)15; }
+size_t stub_png_length(uint64_t h, const mvhp_output_geometry_t *g) { return 64 + (size_t)(h % (mvhp::png_max_bytes((int)g->out_w, (int)g->out_h) - 64)); }
 size_t stub_jpeg_length(uint64_t h, size_t raw) { return 32 + (size_t)(h % (raw / 2)); }
 bool stub_jpeg_too_big(uint64_t h) { return h % 5 == 0; }
 int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &done, std::string &err)
@@ -146,8 +153,8 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
     const mvhp_stream_params_t *p = j.params;
     const mvhp_output_geometry_t *g = j.geom;
     const bool resample = j.out_yuv || j.out_rgb;
-    (j.jpeg ? g_jpeg_calls : resample ? g_geometry_calls : g_recon_calls)++;
-    if (!j.d_yuv || (!j.jpeg && (g != nullptr) != resample)) { err = "stub: geometry launch without buffers"; return MVHP_FAILURE; }
+    (j.jpeg ? g_jpeg_calls : j.png ? g_png_calls : resample ? g_geometry_calls : g_recon_calls)++;
+    if (!j.d_yuv || (!j.jpeg && !j.png && (g != nullptr) != resample)) { err = "stub: geometry launch without buffers"; return MVHP_FAILURE; }
     if (j.turns < 0 || j.turns > 3 || (!j.turns && j.mid_yuv) || (j.turns && (!g || !resample))) { err = "stub: orientation without buffers"; return MVHP_FAILURE; }
     if (j.turns) {
         const uint32_t w0 = (j.turns & 1) ? g->out_h : g->out_w, h0 = (j.turns & 1) ? g->out_w : g->out_h;   // before the turn
@@ -161,6 +168,13 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
         err = "stub: JPEG launch without buffers or parameters";
         return MVHP_FAILURE;
     }
+    // (PNG: RGB present -- fused where the pictures are of the coded size, a pass's target exactly where they are not -- no planes)
+    if (j.png && (!g || j.jpeg || !j.blob || !j.table || j.out_yuv || j.png->reserved || !(resample ? j.out_rgb : j.d_rgb) ||
+                  (j.out_rgb != nullptr) != (j.turns != 0 || g->out_w != p->width_mbs * 16 || g->out_h != p->height_mbs * 16))) {
+        err = "stub: PNG launch without buffers or parameters";
+        return MVHP_FAILURE;
+    }
+    if (j.png && j.blob_cap != (size_t)j.n * stub_png_room(g)) { err = "stub: the blob is not n longest files long"; return MVHP_FAILURE; }
     const int n = j.n;
     const size_t pb = mvhp_packed_frame_bytes(p), yb = mvhp_yuv_frame_bytes(p), rb = mvhp_rgb_frame_bytes(p);
     const size_t gy = mvhp_geometry_yuv_bytes(g), gr = mvhp_geometry_rgb_bytes(g);
@@ -183,7 +197,7 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
             memset(coded, 0x5a, yb);
             memcpy(coded, &h, sizeof(h));
         }
-        if (j.d_rgb && !g) {
+        if (j.d_rgb && (!g || j.png)) {
             memset(j.d_rgb + (size_t)i * rb, 0xa5, rb);
             memcpy(j.d_rgb + (size_t)i * rb + 8, &h, sizeof(h));
         }
@@ -210,6 +224,15 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
             }
             j.table[i] = e;
         }
+        if (j.png) {
+            const uint8_t *src = resample ? j.out_rgb + (size_t)i * gr : j.d_rgb + (size_t)i * rb;
+            const size_t len = stub_png_length(h, g);
+            memset(j.blob + pos, 0x3d, len);
+            memcpy(j.blob + pos, src + 8, 8);
+            j.blob[pos + len - 1] = kLastPng;
+            j.table[i] = mvhp_jpeg_entry_t{pos, (uint32_t)len, MVHP_PNG_OK};
+            pos = (pos + len + 15) & ~(size_t)15;
+        }
         if (j.stats) {
             mvhp_luma_stats_t st{};
             const size_t Wp = (size_t)p->width_mbs * 16;
@@ -233,7 +256,7 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
 
 mvengine::DeviceApi g_stub = {stub_device_count, stub_host_alloc, stub_host_free, stub_ctx_create, stub_ctx_destroy,
                                     stub_dev_alloc, stub_dev_free, stub_dev_free_bytes, stub_copy_n, stub_copy_n, stub_run_batch,
-                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT,
+                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_PNG,
                                     nullptr, nullptr};   // (no placed arena on the stub device)
 
 uint64_t picture_checksum(const mvhp_stream &s, int idr)
@@ -370,6 +393,45 @@ struct CheckJ {
         memcpy(&got, rgb, 8);
         if (got != h || rgb[8] != 0x3c || rgb[len - 1] != kLastJpeg) c.bad++;
         c.bytes += len;
+        c.ok++;
+        return 1;
+    }
+};
+
+// sink of the PNG mode: no planes, the right picture's file in `rgb`, its length in reserved[0]; a picture fails only where its
+// geometry cannot be formed, or -- `no_op` -- where the device table lacks the operation
+struct CheckP {
+    const mvhp_stream *s = nullptr;
+    mvhp_output_request_t req{};
+    bool scored = false;   // the request has MVHP_OUTPUT_SCORE: reserved[1] is the picture's score (the score mode checks its value)
+    int calls = 0, ok = 0, failed = 0, bad = 0, next_seq = 0, no_op = 0;
+    uint64_t bytes = 0;   // what the downloader had to move: 16 per picture in a batch + the files
+    std::vector<int> order;
+    static int sink(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *, const mvhp_output_geometry_t *g,
+                    const uint8_t *yuv, const uint8_t *rgb)
+    {
+        CheckP &c = *static_cast<CheckP *>(user);
+        c.calls++;
+        if (seq != c.next_seq || idr != c.order[(size_t)seq] || !g || yuv) c.bad++;
+        c.next_seq = seq + 1;
+        mvhp_output_geometry_t want;
+        const bool formed = mvhp_output_geometry(c.s, idr, &c.req, &want) == MVHP_SUCCESS;
+        const uint64_t h = picture_checksum(*c.s, idr);
+        if (rc != MVHP_SUCCESS) {
+            c.failed++;
+            if (err && strstr(err, "no PNG operation")) c.no_op++;
+            else if (!err || !*err || rgb || formed) c.bad++;
+            return 0;
+        }
+        if (!formed || !rgb) { c.bad++; return 0; }
+        const size_t len = stub_png_length(h, &want);
+        want.reserved[0] = (uint32_t)len;
+        if (c.scored) want.reserved[1] = g->reserved[1];
+        if (memcmp(&want, g, sizeof(want)) != 0) { c.bad++; return 0; }
+        uint64_t got = 0;
+        memcpy(&got, rgb, 8);
+        if (got != h || rgb[8] != 0x3d || rgb[len - 1] != kLastPng) c.bad++;
+        c.bytes += sizeof(mvhp_jpeg_entry_t) + len;
         c.ok++;
         return 1;
     }
@@ -983,6 +1045,81 @@ int main(int argc, char **argv)
                 mvhp_engine_destroy(e);
             }
             printf("JPEG MODE DONE\n");
+        }
+        if (argc > 5 && !strcmp(argv[5], "png")) {   // ---- PNG mode: MVHP_OUT_PNG against the stub's PNG operation ----
+            auto run_png = [&](const char *name, mvhp_engine_opts_t o, const mvhp_stream &st, const std::vector<int> &order, int wanted,
+                               const mvhp_output_request_t &req, CheckP &c, mvhp_decode_stats_t &stats) {
+                mvhp_engine_t *e = nullptr;
+                if (mvhp_engine_create(&o, &e) != MVHP_SUCCESS) { failures++; return MVHP_FAILURE; }
+                c.s = &st; c.req = req; c.req.flags &= ~MVHP_OUTPUT_SCORE; c.scored = (req.flags & MVHP_OUTPUT_SCORE) != 0; c.order = order;
+                const int rc = mvhp_engine_decode_ex(e, &st, order.data(), (int)order.size(), wanted, MVHP_OUT_PNG, &req, CheckP::sink, &c, &stats);
+                mvhp_engine_destroy(e);
+                printf("%-28s flags=%#x rc=%d issued=%u ok=%u failed=%u batches=%u geometry=%u requeued=%u d2h=%llu\n", name, req.flags, rc,
+                       stats.pictures_issued, stats.pictures_ok, stats.pictures_failed, stats.batches, stats.geometry_launches,
+                       stats.batches_requeued, (unsigned long long)stats.d2h_bytes);
+                return rc;
+            };
+            std::vector<int> order;
+            for (int k = 0; k < 3 * n3; k++) order.push_back(k % n3);
+            int unformed = 0;
+            for (int idr : order) {
+                mvhp_output_geometry_t g;
+                if (mvhp_output_geometry(&s3, idr, &box, &g) != MVHP_SUCCESS) unformed++;
+            }
+            mvhp_output_request_t turned = crop, turned_box = box;
+            turned.flags |= MVHP_OUTPUT_ROTATE(1);
+            turned_box.flags |= MVHP_OUTPUT_ROTATE(3);
+            for (int contexts = 1; contexts <= 3; contexts++)
+                for (const mvhp_output_request_t &req : {mvhp_output_request_t{0, 0, 0, 0}, crop, box, turned, turned_box}) {
+                    mvhp_engine_opts_t o = base; o.contexts = contexts; o.chunk_pictures = 2; o.batch_pictures = contexts == 1 ? 64 : 3;
+                    o.fail_context = contexts == 3 ? 0 : -1;   // three contexts: the first batch of context 0 fails and is re-queued
+                    CheckP c; mvhp_decode_stats_t st;
+                    const int before = g_png_calls, others_before = g_recon_calls + g_geometry_calls + g_jpeg_calls;
+                    EXPECT(run_png("png", o, s3, order, (int)order.size(), req, c, st) == MVHP_SUCCESS);
+                    EXPECT(c.bad == 0 && c.no_op == 0 && c.calls == (int)order.size() && c.ok + c.failed == c.calls && c.ok == (int)st.pictures_ok);
+                    if (req.flags & MVHP_OUTPUT_BOX) EXPECT(c.failed == unformed);
+                    if (!req.flags) EXPECT(st.geometry_launches == 0 && c.failed == 0);
+                    EXPECT(st.d2h_bytes == c.bytes && (int)st.batches == g_png_calls - before);
+                    EXPECT(g_recon_calls + g_geometry_calls + g_jpeg_calls == others_before);   // every launch of a PNG call is the PNG operation
+                    EXPECT((int)st.batches_requeued == (contexts == 3 ? 1 : 0));
+                }
+            EXPECT(unformed >= 1);
+            {   // `wanted` caps the call
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 4;
+                CheckP c; mvhp_decode_stats_t st;
+                EXPECT(run_png("png wanted = 5", o, s3, order, 5, crop, c, st) == MVHP_SUCCESS);
+                EXPECT(c.bad == 0 && c.ok == 5 && st.pictures_ok == 5 && st.pictures_issued < order.size());
+            }
+            {   // scores travel beside the files: 32 more bytes per delivered picture, the same files
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 3;
+                mvhp_output_request_t scored = crop;
+                scored.flags |= MVHP_OUTPUT_SCORE;
+                CheckP c; mvhp_decode_stats_t st;
+                const int stats0 = g_stats_calls;
+                EXPECT(run_png("png + scores", o, s3, order, (int)order.size(), scored, c, st) == MVHP_SUCCESS);
+                EXPECT(c.bad == 0 && c.ok > 0 && c.ok + c.failed == c.calls && g_stats_calls - stats0 == (int)st.batches);
+                EXPECT(st.d2h_bytes == c.bytes + 32ull * (uint64_t)c.ok);
+            }
+            {   // a device table without the operation: every picture fails with a message, nothing is launched
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 3;
+                g_stub.caps &= ~mvengine::CAP_PNG;
+                CheckP c; mvhp_decode_stats_t st;
+                const int before = g_png_calls;
+                EXPECT(run_png("png without the operation", o, s3, order, (int)order.size(), mvhp_output_request_t{0, 0, 0, 0}, c, st) != MVHP_SUCCESS);
+                EXPECT(c.bad == 0 && c.ok == 0 && c.no_op == (int)order.size() && g_png_calls == before);
+                g_stub.caps |= mvengine::CAP_PNG;
+            }
+            {   // the plain sink cannot take a file's length, and a call delivers one kind of file: refused
+                mvhp_engine_opts_t o = base; o.contexts = 1;
+                mvhp_engine_t *e = nullptr;
+                EXPECT(mvhp_engine_create(&o, &e) == MVHP_SUCCESS);
+                Check c; CheckP cp; mvhp_decode_stats_t st;
+                EXPECT(mvhp_engine_decode(e, &s3, o3.data(), n3, n3, MVHP_OUT_PNG, Check::sink, &c, &st) == MVHP_FAILURE);
+                EXPECT(mvhp_engine_decode_ex(e, &s3, o3.data(), n3, n3, MVHP_OUT_PNG | MVHP_OUT_JPEG, nullptr, CheckP::sink, &cp, &st) == MVHP_FAILURE);
+                EXPECT(cp.calls == 0);
+                mvhp_engine_destroy(e);
+            }
+            printf("PNG MODE DONE\n");
         }
         if (argc > 5 && !strcmp(argv[5], "orient")) {   // ---- orient mode: MVHP_OUTPUT_ORIENT / _ROTATE against the stub's turn ----
             auto run_o = [&](const char *name, mvhp_engine_opts_t o, const mvhp_stream &st, const std::vector<int> &order, int mask,
