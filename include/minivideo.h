@@ -30,6 +30,15 @@
  *     at the turned size (1080 x 1920 for a 90-degree 1920 x 1080 clip), a MINIVIDEO_THUMBNAIL box is the box of the turned
  *     picture, file names do not change; 0, the empty string and a rotation that comes to 0 are the files without the switch.
  *     Any other value ("45", "90x") is not ignored: minivideo_decode() returns FAILURE with a message before any device work;
+ *   - opt-in, outside the reference's behaviour (which parses the SPS's VUI and only traces it, h264_parameterset.c:1318-1350)
+ *     and independent of the switches above: MINIVIDEO_ASPECT=1 applies the VUI's sample aspect ratio -- the pictures are
+ *     written with square samples, one axis of the cropped picture shrunk on the GPU (1440 x 1080 at SAR 4:3: 1440 x 810; implies
+ *     MINIVIDEO_CROP; a MINIVIDEO_THUMBNAIL box is fitted to that size); MINIVIDEO_COLOR=auto|bt601|bt709|bt601-full|bt709-full
+ *     makes the RGB formats (png, bmp, tga, also compressed PNG) from the final planes by the stream's own matrix, range and
+ *     chroma siting ("auto": matrix_coefficients 1 = BT.709, 5 / 6 = BT.601, otherwise by size; video_full_range_flag;
+ *     chroma_sample_loc_type) or by the named matrix and range, instead of the reference's BT.601 limited-range formula; yuv and
+ *     jpg files are not touched.  0 and the empty string are the files without the switch; any other value is not ignored:
+ *     minivideo_decode() returns FAILURE with a message before any device work;
  *   - PICTURE_JPG is written as PNG, as a reference built without libjpeg does (export.c:644-690).  Opt-in, outside the
  *     reference's behaviour and independent of the switches above: with MINIVIDEO_JPEG=1 PICTURE_JPG writes <name>[_k].jpg,
  *     baseline JFIF files coded on the GPU from the 4:2:0 planes as export.c:341-430 does with libjpeg (2x2 / 1x1 / 1x1

@@ -201,6 +201,24 @@ MVHP_EXPORT int  mvhp_stream_idr_count(const mvhp_stream_t *s);
  * reference reads the matrix, traces it and drops it (demuxer/mp4/mp4.c:1167-1197).  Information only: nothing turns unless an
  * output request asks for it ("Orientation" below). */
 MVHP_EXPORT int  mvhp_stream_rotation(const mvhp_stream_t *s);
+/* What the VUI of the SPS in force for IDR picture `idr` says about display (E.1.1, up to and excluding timing_info; the
+ * reference parses these fields and only traces them, h264_parameterset.c:1318-1350).  sar_w : sar_h is the sample aspect ratio
+ * after Table E-1 (aspect_ratio_idc 1..16) or the transmitted pair (idc 255), reduced by their gcd; 0 : 0 = unspecified (no VUI,
+ * no aspect_ratio_info, idc 0 or 17..254, or a zero term).  matrix_coefficients is 2 ("unspecified") and chroma_loc 0 when the
+ * stream does not carry them; chroma_loc is chroma_sample_loc_type_top_field (frames only).  A VUI that ends early or carries a
+ * chroma_sample_loc_type above 5 never fails the SPS: every field is then "unspecified" and vui_present stays 1.  Information
+ * only: nothing changes unless an output request asks for it ("Display aspect and colour" below).  MVHP_FAILURE: the picture has
+ * no parameter sets. */
+typedef struct mvhp_display_info {
+    uint32_t sar_w, sar_h;
+    uint32_t vui_present;          /* vui_parameters_present_flag                                             */
+    uint32_t signal_present;       /* video_signal_type_present_flag                                          */
+    uint32_t full_range;           /* video_full_range_flag (0 when absent)                                   */
+    uint32_t matrix_coefficients;  /* Table E-5; 2 when absent                                                */
+    uint32_t chroma_loc;           /* chroma_sample_loc_type_top_field, 0..5; 0 when absent                   */
+    uint32_t reserved;
+} mvhp_display_info_t;
+MVHP_EXPORT int  mvhp_stream_display(const mvhp_stream_t *s, int idr, mvhp_display_info_t *out);
 /* Parameters in force for IDR picture `idr` (valid after mvhp_stream_open). */
 MVHP_EXPORT int  mvhp_stream_params(const mvhp_stream_t *s, int idr, mvhp_stream_params_t *out);
 /* Entropy-decode IDR picture `idr` into `packed` (mvhp_packed_frame_bytes()).
@@ -272,7 +290,8 @@ MVHP_EXPORT int  mvhp_recon_stages_dev(mvhp_ctx_t *ctx, const mvhp_stream_params
  *         x = 2 left, y = 2 top, w = 16 W - 2 (left + right), h = 16 H - 2 (top + bottom); chroma is the same rectangle halved.
  *   box:  the cropped picture fitted into box_w x box_h (DESIGN.md 3 "Output geometry": aspect kept, even sides, never
  *         enlarged) by an integer area-average filter that is exact for D = S (crop only is the same pass).
- * Thumbnails assume square samples (VUI sample aspect ratio is not parsed).
+ * Crop and box treat samples as square: a 1440 x 1080 SAR 4:3 picture keeps its 4:3 grid.  MVHP_OUTPUT_ASPECT (below) applies the
+ * VUI's sample aspect ratio (mvhp_stream_display) first.
  * ------------------------------------------------------------------------- */
 typedef struct mvhp_output_geometry {
     uint32_t crop_x, crop_y, crop_w, crop_h;   /* luma rectangle of the coded picture that is kept (all even)          */
@@ -292,6 +311,27 @@ typedef struct mvhp_output_geometry {
 #define MVHP_OUTPUT_ROTATE_SHIFT 4
 #define MVHP_OUTPUT_ROTATE_MASK  0x30u
 #define MVHP_OUTPUT_ROTATE(q) (((uint32_t)(q) & 3u) << MVHP_OUTPUT_ROTATE_SHIFT)
+/* Display aspect (opt-in; DESIGN.md 3 "Display aspect and colour"): MVHP_OUTPUT_ASPECT (implies MVHP_OUTPUT_CROP) makes the
+ * samples of the output square.  With the crop cw x ch and the stream's sample aspect ratio a : b (1 : 1 when unspecified), in
+ * 64-bit arithmetic, one axis shrinks and nothing is ever enlarged:
+ *     a > b:  out_w = cw, out_h = max(2, 2 floor((ch b + a) / (2 a)))        a < b:  out_h = ch, out_w = max(2, 2 floor((cw a + b) / (2 b)))
+ * (1440 x 1080 at 4:3 -> 1440 x 810; 720 x 576 at 12:11 -> 720 x 528; 720 x 480 at 10:11 -> 654 x 480).  A box is fitted to that
+ * size afterwards (1440 x 1080 at 4:3 in 320 x 320 -> 320 x 180), a turn exchanges the sides last; crop_* do not change.  The
+ * resample pass filters each axis with its own ratio, so it is the pass of a box with that output size.
+ * Colour (opt-in): MVHP_OUTPUT_COLOR makes the RGB a call delivers (MVHP_OUT_RGB, MVHP_OUT_RGB_ONLY, MVHP_OUT_PNG) with
+ * mvhp_color_dev from the FINAL planes -- behind the crop, the box and the turn -- instead of the reference's BT.601
+ * limited-range formula; the parameters are mvhp_color_resolve() of the picture's mvhp_stream_display() under the mode
+ * MVHP_OUTPUT_COLOR_MODE(m) (bits 8-10: 0 auto, 1 BT.601 limited, 2 BT.709 limited, 3 BT.601 full, 4 BT.709 full), except that
+ * pictures a resample pass SCALED take MVHP_CHROMA_CENTER whatever the stream says (an area average of chroma is centred on its
+ * 2x2 luma cell; a turned picture keeps the stream's siting as read along its own rows -- an approximation).  Planes and JPEG
+ * files are not affected (JFIF defines what its planes mean); a call that delivers no RGB ignores the flag and launches nothing.
+ * A batch holds pictures of one geometry and one resolved colour setting.  Without these flags every path, launch, buffer and
+ * byte is what it is without them. */
+#define MVHP_OUTPUT_ASPECT 0x800u   /* (0x40 stays an unknown flag: the engine harness pins it as the one a request is refused for) */
+#define MVHP_OUTPUT_COLOR  0x80u
+#define MVHP_OUTPUT_COLOR_MODE_SHIFT 8
+#define MVHP_OUTPUT_COLOR_MODE_MASK  0x700u
+#define MVHP_OUTPUT_COLOR_MODE(m) (((uint32_t)(m) & 7u) << MVHP_OUTPUT_COLOR_MODE_SHIFT)
 typedef struct mvhp_output_request {
     uint32_t flags;           /* MVHP_OUTPUT_*; 0 = the coded size (what the reference writes)                  */
     uint32_t box_w, box_h;
@@ -312,6 +352,9 @@ MVHP_EXPORT int    mvhp_output_geometry(const mvhp_stream_t *s, int idr, const m
                                         mvhp_output_geometry_t *out);
 /* The size rule alone: cw x ch (even) fitted into bw x bh (each >= 2) -> *ow x *oh. */
 MVHP_EXPORT int    mvhp_geometry_fit(uint32_t cw, uint32_t ch, uint32_t bw, uint32_t bh, uint32_t *ow, uint32_t *oh);
+/* The aspect rule alone (MVHP_OUTPUT_ASPECT above): cw x ch (even, >= 2) with sample aspect ratio sar_w : sar_h (0 in either: 1 : 1)
+ * -> *ow x *oh. */
+MVHP_EXPORT int    mvhp_geometry_aspect(uint32_t cw, uint32_t ch, uint32_t sar_w, uint32_t sar_h, uint32_t *ow, uint32_t *oh);
 /* Bytes of one output picture: planar Y | Cb | Cr of out_w x out_h, and interleaved RGB8. */
 MVHP_EXPORT size_t mvhp_geometry_yuv_bytes(const mvhp_output_geometry_t *g);
 MVHP_EXPORT size_t mvhp_geometry_rgb_bytes(const mvhp_output_geometry_t *g);
@@ -340,6 +383,52 @@ MVHP_EXPORT int    mvhp_resample_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t
 MVHP_EXPORT int    mvhp_orient_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g, int quarter_turns,
                                    uint32_t src_flags, const uint8_t *d_src, int n, uint8_t *d_yuv_out, uint8_t *d_rgb_out,
                                    void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Colour conversion (opt-in; DESIGN.md 3 "Display aspect and colour"; color_convert.hip): RGB from planar 4:2:0 pictures by the
+ * matrix, range and chroma siting the stream names, in integers only -- the bytes are a function of the samples and the three
+ * parameters (tests/color_ref.py restates them).
+ *   Chroma in sixteenths.  For luma (x, y), j = y >> 1, k = x >> 1, chroma indices clamped at the plane's edges:
+ *     vertical:            y even: rows (j-1, j) weights (1, 3);           y odd: rows (j, j+1) weights (3, 1)
+ *     MVHP_CHROMA_LEFT:    x even: column k weight 4;                      x odd: columns (k, k+1) weights (2, 2)
+ *     MVHP_CHROMA_CENTER:  x even: columns (k-1, k) weights (1, 3);        x odd: columns (k, k+1) weights (3, 1)
+ *     c16 = sum of wy wx C (the weights sum to 16, nothing is rounded);    MVHP_CHROMA_NEAREST: c16 = 16 C[j][k]
+ *   Colour.  y' = 16 cy (Y - yoff), cb = Cb16 - 2048, cr = Cr16 - 2048, >> arithmetic:
+ *     R = clamp8((y' + crv cr + 2^17) >> 18)   G = clamp8((y' - gcb cb - gcr cr + 2^17) >> 18)   B = clamp8((y' + cbu cb + 2^17) >> 18)
+ *   Coefficients {cy, crv, cbu, gcb, gcr, yoff} = round(2^14 x) of the exact rationals of (Kr, Kb) = (0.299, 0.114) for BT.601
+ *   and (0.2126, 0.0722) for BT.709, times 255/219 (luma) and 255/224 (chroma) for limited range (yoff 16, else 0):
+ *   mvhp_color_coefficients().
+ * ------------------------------------------------------------------------- */
+#define MVHP_MATRIX_BT601 0
+#define MVHP_MATRIX_BT709 1
+#define MVHP_CHROMA_NEAREST 0
+#define MVHP_CHROMA_LEFT    1
+#define MVHP_CHROMA_CENTER  2
+typedef struct mvhp_color_params {
+    int32_t matrix;       /* MVHP_MATRIX_*            */
+    int32_t full_range;   /* 0 limited (16..235 / 16..240), 1 full (0..255) */
+    int32_t siting;       /* MVHP_CHROMA_*            */
+    int32_t reserved;     /* 0                        */
+} mvhp_color_params_t;
+/* out = {cy, crv, cbu, gcb, gcr, yoff}.  Host only.  MVHP_FAILURE: a matrix or range outside the values above. */
+MVHP_EXPORT int    mvhp_color_coefficients(int matrix, int full_range, int32_t out[6]);
+/* The parameters for pictures of `coded_w` x `coded_h` whose stream says `d` (NULL: nothing).  Host only.
+ *   mode 0 (auto): matrix_coefficients 1 -> BT.709; 5 or 6 -> BT.601; anything else or absent -> BT.709 when coded_w >= 1280 or
+ *     coded_h > 576, else BT.601 (GBR, YCgCo, BT.2020 and the other codes are not supported and take this fallback); full range
+ *     from video_full_range_flag when the signal type is present, else limited;
+ *   mode 1 .. 4: BT.601 limited, BT.709 limited, BT.601 full, BT.709 full, whatever the stream says;
+ *   siting, every mode: chroma_loc even -> MVHP_CHROMA_LEFT, odd -> MVHP_CHROMA_CENTER (types 2..5 keep only their horizontal
+ *     part: the vertical weights are those of types 0 and 1 -- an approximation).
+ * MVHP_FAILURE: a mode outside 0..4 or no `out`. */
+MVHP_EXPORT int    mvhp_color_resolve(const mvhp_display_info_t *d, uint32_t coded_w, uint32_t coded_h, int mode, mvhp_color_params_t *out);
+/* n dense planar pictures of g->out_w x g->out_h (d_yuv, 4-byte aligned, as mvhp_resample_dev and mvhp_orient_dev leave them;
+ * planes of the coded size go with a geometry of the coded size) -> n dense RGB8 pictures (d_rgb_out, 4-byte aligned).  Only
+ * out_w and out_h of g are read.  n = 0 does nothing; n < 0, odd or zero sizes or sizes above 16384, enum values outside the
+ * ones above, a non-zero `reserved` and misaligned or NULL pointers are refused (MVHP_FAILURE) before anything is launched.
+ * Asynchronous on `stream` (NULL = the context's own).  Nothing is shared between workgroups, no kernel waits and nothing
+ * survives a launch: safe under stream capture, and two calls on two streams do not meet. */
+MVHP_EXPORT int    mvhp_color_dev(mvhp_ctx_t *ctx, const mvhp_output_geometry_t *g, const mvhp_color_params_t *params,
+                                  const uint8_t *d_yuv, int n, uint8_t *d_rgb_out, void *stream);
 
 /* ---------------------------------------------------------------------------
  * JPEG output (opt-in; DESIGN.md 3 "JPEG output"): baseline sequential JFIF files made on the device from planar pictures, the

@@ -209,6 +209,10 @@ struct GenCfg {
     // frame cropping (mvgen_stream_crop; 0 = frame_cropping_flag 0, as every other stream)
     int n_crops = 0;
     const int32_t *crops = nullptr;         // n_crops x {left, right, top, bottom}
+    // VUI (mvgen_stream_vui; 0 = vui_parameters_present_flag 0, as every other stream)
+    int n_vuis = 0;
+    const int32_t *vuis = nullptr;          // n_vuis x MVGEN_VUI_FIELDS (see mvgen_stream_vui)
+    int vui_keep_bits = -1;                 // >= 0: the SPS ends after this many bits of vui_parameters() (a truncated SPS)
 };
 
 struct MbSyntax {
@@ -918,10 +922,47 @@ struct Gen {
         } else {
             bw.bit(0);           // frame_cropping_flag
         }
+        if (cfg.n_vuis > 0) {    // mvgen_stream_vui: SPS k carries record k % n_vuis
+            bw.bit(1);           // vui_parameters_present_flag
+            BitWriter v;
+            write_vui(v, cfg.vuis + 16 * (sps_written % cfg.n_vuis));
+            const int keep = cfg.vui_keep_bits >= 0 && cfg.vui_keep_bits < v.nbits ? cfg.vui_keep_bits : v.nbits;
+            for (int i = 0; i < keep; i++) bw.bit((v.bytes[(size_t)i >> 3] >> (7 - (i & 7))) & 1);
+        } else {
+            bw.bit(0);           // vui_parameters_present_flag
+        }
         sps_written++;
-        bw.bit(0);               // vui_parameters_present_flag
         bw.trailing();
         emit_nal(out, 3, 7, bw.bytes);
+    }
+    // vui_parameters() (E.1.1) of one record: {aspect_present, idc, sar_w, sar_h, overscan (0 absent, 1 / 2 present with
+    // overscan_appropriate_flag 0 / 1), signal_present, video_format, full_range, colour_description_present, primaries, transfer,
+    // matrix, chroma_loc_present, loc_top, loc_bottom, timing (1: timing_info with fixed_frame_rate_flag)}; no HRD, no
+    // pic_struct, no bitstream_restriction
+    static void write_vui(BitWriter &bw, const int32_t *r)
+    {
+        bw.bit(r[0] != 0);
+        if (r[0]) {
+            bw.bits((uint32_t)r[1], 8);
+            if (r[1] == 255) { bw.bits((uint32_t)r[2], 16); bw.bits((uint32_t)r[3], 16); }
+        }
+        bw.bit(r[4] != 0);
+        if (r[4]) bw.bit(r[4] == 2);
+        bw.bit(r[5] != 0);
+        if (r[5]) {
+            bw.bits((uint32_t)r[6], 3);
+            bw.bit(r[7] != 0);
+            bw.bit(r[8] != 0);
+            if (r[8]) { bw.bits((uint32_t)r[9], 8); bw.bits((uint32_t)r[10], 8); bw.bits((uint32_t)r[11], 8); }
+        }
+        bw.bit(r[12] != 0);
+        if (r[12]) { bw.ue((uint32_t)r[13]); bw.ue((uint32_t)r[14]); }
+        bw.bit(r[15] != 0);      // timing_info_present_flag
+        if (r[15]) { bw.bits(1001, 32); bw.bits(60000, 32); bw.bit(1); }
+        bw.bit(0);               // nal_hrd_parameters_present_flag
+        bw.bit(0);               // vcl_hrd_parameters_present_flag
+        bw.bit(0);               // pic_struct_present_flag
+        bw.bit(0);               // bitstream_restriction_flag
     }
     void write_pps(std::vector<uint8_t> &out)
     {
@@ -1119,6 +1160,35 @@ size_t mvgen_stream_crop(const mvgen_cfg_t *c, int32_t n_crops, const int32_t *c
     GenCfg g = to_cfg(c);
     g.n_crops = n_crops;
     g.crops = crops;
+    return run_generator(g, out, cap, packed, nullptr);
+}
+
+// mvgen_stream plus VUI (and, with n_crops > 0, the frame cropping of mvgen_stream_crop): SPS number k writes
+// vui_parameters_present_flag = 1 and record k % n_vuis of `vuis`, 16 int32 each: {aspect_ratio_info_present, aspect_ratio_idc,
+// sar_width, sar_height (idc 255), overscan (0 absent, 1 / 2 present, appropriate 0 / 1), video_signal_type_present, video_format,
+// video_full_range, colour_description_present, colour_primaries, transfer_characteristics, matrix_coefficients,
+// chroma_loc_info_present, loc_type_top, loc_type_bottom, timing_info_present}.  keep_bits >= 0 ends every SPS after that many
+// bits of vui_parameters(): a truncated SPS, for the front end's tolerance.  The macroblocks and records are those of
+// mvgen_stream with the same configuration.
+__attribute__((visibility("default")))
+size_t mvgen_stream_vui(const mvgen_cfg_t *c, int32_t n_vuis, const int32_t *vuis, int32_t keep_bits, int32_t n_crops,
+                        const int32_t *crops, uint8_t *out, size_t cap, uint8_t *packed)
+{
+    if (!c || c->width_mbs <= 0 || c->height_mbs <= 0 || c->n_frames <= 0) return 0;
+    if (c->profile_idc != 66 && c->profile_idc != 77 && c->profile_idc != 100) return 0;
+    if (c->cabac && c->profile_idc == 66) return 0;
+    if (c->transform8x8 && c->profile_idc != 100) return 0;
+    if (n_vuis < 1 || !vuis || n_crops < 0 || (n_crops > 0 && !crops)) return 0;
+    for (int i = 0; i < 16 * n_vuis; i++)
+        if (vuis[i] < 0 || vuis[i] > 65535) return 0;
+    for (int i = 0; i < 4 * n_crops; i++)
+        if (crops[i] < 0) return 0;
+    GenCfg g = to_cfg(c);
+    g.n_vuis = n_vuis;
+    g.vuis = vuis;
+    g.vui_keep_bits = keep_bits;
+    g.n_crops = n_crops;
+    g.crops = n_crops > 0 ? crops : nullptr;
     return run_generator(g, out, cap, packed, nullptr);
 }
 

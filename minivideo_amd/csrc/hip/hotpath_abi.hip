@@ -522,6 +522,42 @@ MVHP_EXPORT int mvhp_orient_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p, co
     return MVHP_SUCCESS;
 }
 
+MVHP_EXPORT int mvhp_color_dev(mvhp_ctx_t *c, const mvhp_output_geometry_t *g, const mvhp_color_params_t *cp, const uint8_t *d_yuv, int n,
+                               uint8_t *d_rgb_out, void *stream)
+{
+    if (!c || !g || !cp || !d_yuv || !d_rgb_out || n < 0 || ((uintptr_t)d_yuv & 3) || ((uintptr_t)d_rgb_out & 3)) {
+        set_err("mvhp_color_dev: invalid argument");
+        return MVHP_FAILURE;
+    }
+    if (((g->out_w | g->out_h) & 1u) || g->out_w < 2 || g->out_h < 2 || g->out_w > 16384 || g->out_h > 16384) {
+        set_err("mvhp_color_dev: pictures of %u x %u (even sides of 2 to 16384)", g->out_w, g->out_h);
+        return MVHP_FAILURE;
+    }
+    int32_t k[6];
+    if (cp->siting < MVHP_CHROMA_NEAREST || cp->siting > MVHP_CHROMA_CENTER || cp->reserved != 0 ||
+        mvhp_color_coefficients(cp->matrix, cp->full_range, k) != MVHP_SUCCESS) {
+        set_err("mvhp_color_dev: parameters {matrix %d, full_range %d, siting %d} are not ones the header names", cp->matrix, cp->full_range, cp->siting);
+        return MVHP_FAILURE;
+    }
+    if (n == 0) return MVHP_SUCCESS;
+    HIP_TRY(hipSetDevice(c->device));
+    mvhp::ColorConvertArgs a;
+    a.w = (int)g->out_w;
+    a.h = (int)g->out_h;
+    a.n = n;
+    a.yuv = d_yuv;
+    a.yuv_end = d_yuv + (((size_t)n * ((size_t)a.w * a.h * 3 / 2)) & ~(size_t)3);
+    a.rgb = d_rgb_out;
+    a.siting = cp->siting;
+    a.ymul = 16 * k[0]; a.crv = k[1]; a.cbu = k[2]; a.gcb = k[3]; a.gcr = k[4]; a.yoff = k[5];
+    // chroma rows per workgroup: the rule of the crop copy and the turn (fewer where the launch would leave CUs idle)
+    int band = 8;
+    while (band > 1 && (double)n * ((a.h / 2 + band - 1) / band) < 4.0 * c->n_cus) band /= 2;
+    a.band = band;
+    HIP_TRY(mvhp::launch_color_convert(a, stream_of(c, stream)));
+    return MVHP_SUCCESS;
+}
+
 static int ensure(void **ptr, size_t *have, size_t need)
 {
     if (*have >= need) return MVHP_SUCCESS;
@@ -915,22 +951,27 @@ int eng_run_batch(DevCtx *d, const mvengine::BatchJob &j, mvengine::BatchDone &d
     if ((resample || j.jpeg || j.png) && !j.geom) { err = "reconstruction: no output geometry"; return MVHP_FAILURE; }
     if (j.jpeg && (!j.blob || !j.table || j.out_rgb)) { err = "reconstruction: invalid JPEG output"; return MVHP_FAILURE; }
     if (j.png && (j.jpeg || !j.blob || !j.table || !(resample ? j.out_rgb : j.d_rgb))) { err = "reconstruction: invalid PNG output"; return MVHP_FAILURE; }
-    if (j.geom && !resample && !j.jpeg && !j.png) { err = "reconstruction: an output geometry without an output buffer"; return MVHP_FAILURE; }
+    if (j.geom && !resample && !j.jpeg && !j.png && !j.color) { err = "reconstruction: an output geometry without an output buffer"; return MVHP_FAILURE; }
+    // colour pass: RGB from the final planes -- out_yuv -> out_rgb behind a pass, else d_yuv -> d_rgb at the coded size
+    if (j.color && (j.jpeg || !j.geom || (resample ? (!j.out_yuv || !j.out_rgb) : !j.d_rgb))) { err = "reconstruction: invalid colour pass"; return MVHP_FAILURE; }
     ENG_TRY(hipSetDevice(c->device));
     ENG_TRY(hipEventRecord(d->ev[2], c->stream));
     if (mvhp_expand_compact_dev(c, p, j.d_compact, j.stride, j.n, j.d_packed, c->stream) != MVHP_SUCCESS) { err = mvhp_last_error(); return MVHP_FAILURE; }
     const bool deblock = (p->flags & MVHP_PARAM_DEBLOCK) != 0;
-    int rc = (resample || j.jpeg) ? launch_all(c, p, j.d_packed, j.n, j.d_yuv, nullptr, c->stream, true, false, deblock)
+    int rc = (resample || j.jpeg || j.color) ? launch_all(c, p, j.d_packed, j.n, j.d_yuv, nullptr, c->stream, true, false, deblock)
                                   : launch_all(c, p, j.d_packed, j.n, j.d_yuv, j.d_rgb, c->stream, true, true, deblock);
-    if (rc == MVHP_SUCCESS && resample && !j.turns) rc = mvhp_resample_dev(c, p, j.geom, j.d_yuv, j.n, j.out_yuv, j.out_rgb, c->stream);
+    uint8_t *const pass_rgb = j.color ? nullptr : j.out_rgb;   // (with a colour pass the passes below make planes only)
+    if (rc == MVHP_SUCCESS && resample && !j.turns) rc = mvhp_resample_dev(c, p, j.geom, j.d_yuv, j.n, j.out_yuv, pass_rgb, c->stream);
     if (rc == MVHP_SUCCESS && j.turns) {   // the geometry before the turn; planes of it first where the box scales
         mvhp_output_geometry_t g0 = *j.geom;
         if (j.turns & 1) std::swap(g0.out_w, g0.out_h);
         if (j.mid_yuv) rc = mvhp_resample_dev(c, p, &g0, j.d_yuv, j.n, j.mid_yuv, nullptr, c->stream);
         if (rc == MVHP_SUCCESS)
             rc = mvhp_orient_dev(c, p, &g0, j.turns, j.mid_yuv ? 0u : MVHP_ORIENT_SRC_CODED, j.mid_yuv ? j.mid_yuv : j.d_yuv, j.n,
-                                 j.out_yuv, j.out_rgb, c->stream);
+                                 j.out_yuv, pass_rgb, c->stream);
     }
+    if (rc == MVHP_SUCCESS && j.color)
+        rc = mvhp_color_dev(c, j.geom, j.color, resample ? j.out_yuv : j.d_yuv, j.n, resample ? j.out_rgb : j.d_rgb, c->stream);
     if (rc == MVHP_SUCCESS && j.jpeg)
         rc = mvhp_jpeg_encode_dev(c, j.geom, j.jpeg, resample ? j.out_yuv : j.d_yuv, j.n, j.blob, j.blob_cap, j.table, c->stream);
     if (rc == MVHP_SUCCESS && j.png)
@@ -993,7 +1034,7 @@ void eng_placed_free(DevCtx *d, void *arena)
 
 const mvengine::DeviceApi g_hip_api = {
     mvhp_device_count, mvhp_host_alloc, mvhp_host_free, eng_ctx_create, eng_ctx_destroy, eng_dev_alloc, eng_dev_free,
-    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_PNG,
+    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_COLOR | mvengine::CAP_PNG,
     eng_placed_alloc, eng_placed_free,
 };
 

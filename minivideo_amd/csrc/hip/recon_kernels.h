@@ -122,6 +122,20 @@ struct OrientArgs {
 };
 hipError_t launch_orient(const OrientArgs &a, hipStream_t stream);
 
+// colour conversion (color_convert.hip): n dense planar pictures of w x h -> n dense RGB8 pictures, by matrix / range
+// coefficients and a chroma siting (include/minivideo_hotpath.h "Colour conversion")
+struct ColorConvertArgs {
+    const uint8_t *yuv;          // n pictures, w * h * 3 / 2 apart, 4-byte aligned
+    const uint8_t *yuv_end;      // end of the last one, rounded down to a dword boundary (nothing behind it is read)
+    uint8_t       *rgb;          // n pictures, w * h * 3 apart, 4-byte aligned
+    int            w, h, n;      // even sides, 2 .. 16384
+    int            siting;       // MVHP_CHROMA_*
+    int            band;         // chroma rows per workgroup (launch_color_convert lowers it to what the LDS holds)
+    int            ymul, yoff;   // 16 * cy, and the luma offset
+    int            crv, cbu, gcb, gcr;
+};
+hipError_t launch_color_convert(const ColorConvertArgs &a, hipStream_t stream);
+
 // baseline JPEG from planar pictures (jpeg_encode.hip): DCT + quantisation, count, scans, write, headers
 struct JpegArgs {
     const uint8_t     *yuv;      // n pictures, planar Y | Cb | Cr of w x h

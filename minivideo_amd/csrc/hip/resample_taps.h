@@ -69,4 +69,24 @@ MVRS_HD int fit(uint32_t cw, uint32_t ch, uint32_t bw, uint32_t bh, uint32_t &ow
     return 1;
 }
 
+// The aspect rule: cw x ch (even) whose samples are a : b as wide as high (0 in either: 1 : 1) -> the size with square samples.
+// One axis shrinks, nothing is enlarged, sides stay even and at least 2.  64-bit: ch * b + a < 2^33 for sides and terms below 2^16
+// (and for any 32-bit values).  0 = bad arguments.
+MVRS_HD int aspect(uint32_t cw, uint32_t ch, uint32_t a, uint32_t b, uint32_t &ow, uint32_t &oh)
+{
+    if (cw < 2 || ch < 2) return 0;
+    ow = cw;
+    oh = ch;
+    if (a == 0 || b == 0 || a == b) return 1;
+    const uint64_t A = a, B = b;
+    if (a > b) {   // wide samples: the height shrinks
+        const uint64_t h = 2 * (((uint64_t)ch * B + A) / (2 * A));
+        oh = h < 2 ? 2u : (uint32_t)h;
+    } else {       // tall samples: the width shrinks
+        const uint64_t w = 2 * (((uint64_t)cw * A + B) / (2 * B));
+        ow = w < 2 ? 2u : (uint32_t)w;
+    }
+    return 1;
+}
+
 } // namespace mvrs

@@ -250,7 +250,7 @@ std::vector<int> select_idrs(const mvhp_stream &s, int picture_number, int mode)
     return sel;
 }
 
-// ---- MINIVIDEO_CROP=1 / MINIVIDEO_THUMBNAIL=<w>x<h> / MINIVIDEO_ROTATE=<auto or angle> (opt-in, include/minivideo.h): the output request of the decode call.
+// ---- MINIVIDEO_CROP=1 / MINIVIDEO_THUMBNAIL=<w>x<h> / MINIVIDEO_ROTATE=<auto or angle> / MINIVIDEO_ASPECT=1 / MINIVIDEO_COLOR=<auto or matrix> (opt-in, include/minivideo.h): the output request of the decode call.
 // A box implies the crop.  false: a malformed value (the call fails before any device work; it is not ignored).
 bool output_request_from_env(mvhp_output_request_t &req, std::string &why)
 {
@@ -266,6 +266,28 @@ bool output_request_from_env(mvhp_output_request_t &req, std::string &why)
         else if (!strcmp(r, "270")) req.flags |= MVHP_OUTPUT_ROTATE(3);
         else if (*r && strcmp(r, "0")) {
             why = std::string("MINIVIDEO_ROTATE='") + r + "' is not auto, 0, 90, 180 or 270";
+            return false;
+        }
+    }
+    // MINIVIDEO_ASPECT=1 (opt-in): the VUI's sample aspect ratio is applied -- square samples out; implies the crop.  0 and the
+    // empty string = unset; anything but 0 or 1 is malformed
+    if (const char *a = getenv("MINIVIDEO_ASPECT")) {
+        if (!strcmp(a, "1")) req.flags |= MVHP_OUTPUT_ASPECT;
+        else if (*a && strcmp(a, "0")) {
+            why = std::string("MINIVIDEO_ASPECT='") + a + "' is not 0 or 1";
+            return false;
+        }
+    }
+    // MINIVIDEO_COLOR=auto|bt601|bt709|bt601-full|bt709-full (opt-in): RGB by the stream's own matrix, range and chroma siting
+    // ("auto") or by a forced matrix and range; 0 and the empty string = unset
+    if (const char *c = getenv("MINIVIDEO_COLOR")) {
+        static const char *const names[5] = {"auto", "bt601", "bt709", "bt601-full", "bt709-full"};
+        int mode = -1;
+        for (int k = 0; k < 5; k++)
+            if (!strcmp(c, names[k])) mode = k;
+        if (mode >= 0) req.flags |= MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE(mode);
+        else if (*c && strcmp(c, "0")) {
+            why = std::string("MINIVIDEO_COLOR='") + c + "' is not auto, bt601, bt709, bt601-full or bt709-full";
             return false;
         }
     }
@@ -692,6 +714,8 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     // decodes in order until `wanted` pictures have been written (h264.c:173-179) or 64 errors in a row (h264.c:181-187)
     // RGB formats are written from the RGB picture alone: the planes stay on the device
     // JPEG files come back finished: only their bytes are downloaded and written
+    // MINIVIDEO_COLOR is about RGB: with planes or JPEG files the request is the one without it
+    if (!want_rgb) req.flags &= ~(MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE_MASK);
     if (jpeg) req.reserved = MVHP_JPEG_REQUEST(std::min(100, std::max(1, picture_quality)), 0);
     // opt-in (MINIVIDEO_SKIP_BLANK=1, outside the parity contract): the same call with every picture's score, pass 1 of 2
     std::vector<ExportSink::Slot> slots;

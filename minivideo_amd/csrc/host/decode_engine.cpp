@@ -83,6 +83,11 @@ bool same_params(const mvhp_stream_params_t &a, const mvhp_stream_params_t &b)
             (memcmp(a.scaling4, b.scaling4, sizeof(a.scaling4)) == 0 && memcmp(a.scaling8, b.scaling8, sizeof(a.scaling8)) == 0));
 }
 
+bool same_color(const mvhp_color_params_t &a, const mvhp_color_params_t &b)
+{
+    return a.matrix == b.matrix && a.full_range == b.full_range && a.siting == b.siting;
+}
+
 bool same_geometry(const mvhp_output_geometry_t &a, const mvhp_output_geometry_t &b)
 {
     return a.crop_x == b.crop_x && a.crop_y == b.crop_y && a.crop_w == b.crop_w && a.crop_h == b.crop_h && a.out_w == b.out_w &&
@@ -183,6 +188,8 @@ struct Wants {
     bool png = false;               // MVHP_OUT_PNG: neither of them; PNG files made on the device from the RGB
     bool score = false;             // MVHP_OUTPUT_SCORE (it changes no picture and no path)
     int turns = 0;                  // quarter turns the request applies (mvhp_output_turns): one value per call
+    bool color = false;             // MVHP_OUTPUT_COLOR in a call that delivers RGB or PNG: the RGB comes from a colour pass over the
+                                    // final planes (which a batch with a geometry then keeps, whether or not they are downloaded)
 };
 // whether a batch of the DELIVERED geometry g, turned by `turns`, has a resample pass in front of the turn
 bool scales_before_turn(const mvhp_output_geometry_t &g, int turns)
@@ -191,7 +198,7 @@ bool scales_before_turn(const mvhp_output_geometry_t &g, int turns)
     return turns != 0 && (w != g.crop_w || h != g.crop_h);
 }
 // what a placed arena and the job's largest batch are planned for: pictures of the coded size, planes and RGB
-constexpr Wants kPlanesAndRgb = {true, true, false, false, false, 0};
+constexpr Wants kPlanesAndRgb = {true, true, false, false, false, 0, false};
 
 // MVHP_OUT_PNG: the room of one picture in the blob -- the longest file there is (every segment stored), so that no picture can be
 // too big, rounded to the 16 bytes files are placed at
@@ -210,7 +217,7 @@ size_t picture_bytes(BufKind k, const mvhp_stream_params_t &p, const mvhp_output
     case kPacked:   return mvhp_packed_frame_bytes(&p);
     case kYuv:      return mvhp_yuv_frame_bytes(&p);
     case kRgb:      return (w.rgb || w.png) && !use_geom ? mvhp_rgb_frame_bytes(&p) : 0;
-    case kOutYuv:   return use_geom && (w.yuv || w.jpeg) ? mvhp_geometry_yuv_bytes(&g) : 0;
+    case kOutYuv:   return use_geom && (w.yuv || w.jpeg || w.color) ? mvhp_geometry_yuv_bytes(&g) : 0;   // (the colour pass reads them)
     case kOutRgb:   return use_geom && (w.rgb || w.png) ? mvhp_geometry_rgb_bytes(&g) : 0;
     case kMidYuv:   return use_geom && scales_before_turn(g, w.turns) ? mvhp_geometry_yuv_bytes(&g) : 0;
     case kJpegBlob: return w.jpeg ? mvhp_geometry_yuv_bytes(&g) : w.png ? png_blob_bytes(g) : 0;
@@ -245,6 +252,7 @@ struct Batch {
     mvhp_stream_params_t params{};
     mvhp_output_geometry_t geom{};   // of every picture of the batch
     bool use_geom = false;           // geom differs from the coded size: the batch has a resample pass
+    mvhp_color_params_t color{};     // MVHP_OUTPUT_COLOR: the resolved setting of every picture of the batch
     std::vector<int> seqs;           // slot -> position in `order`
     int capacity = 0;                // planned pictures (device buffers are sized for it)
     int total = -1;                  // pictures, known once the closing chunk has been issued
@@ -346,6 +354,8 @@ private:
     Wants w_;                                   // (score: taken out of req_.flags)
     mvhp_jpeg_params_t jpeg_{};
     mvhp_png_params_t png_{};
+    int color_mode_ = 0;             // MVHP_OUTPUT_COLOR_MODE of the call
+    mvhp_color_params_t picture_color(int idr, const mvhp_stream_params_t &p, const mvhp_output_geometry_t &g) const;
     mvhp_output_request_t req_{};               // flags 0: pictures of the coded size
     bool stop_ = false;
     bool sink_waiting_ = false;
@@ -476,6 +486,20 @@ bool Engine::picture_geometry(int idr, const mvhp_stream_params_t &p, mvhp_outpu
     }
     use = w_.turns != 0 || !same_geometry(g, coded_geometry(p));   // (a turned picture of the coded size still has a pass)
     return true;
+}
+
+// The colour setting of picture `idr` under MVHP_OUTPUT_COLOR (all zero without it): what the stream says under the call's mode;
+// a picture the resample pass scales takes the centred siting (an area average of chroma is centred on its 2x2 luma cell).
+mvhp_color_params_t Engine::picture_color(int idr, const mvhp_stream_params_t &p, const mvhp_output_geometry_t &g) const
+{
+    mvhp_color_params_t c{};
+    if (!w_.color) return c;
+    mvhp_display_info_t d{};
+    const bool have = mvhp_stream_display(s_, idr, &d) == MVHP_SUCCESS;
+    mvhp_color_resolve(have ? &d : nullptr, p.width_mbs * 16, p.height_mbs * 16, color_mode_, &c);
+    const uint32_t w = (w_.turns & 1) ? g.out_h : g.out_w, h = (w_.turns & 1) ? g.out_w : g.out_h;
+    if (w != g.crop_w || h != g.crop_h) c.siting = MVHP_CHROMA_CENTER;
+    return c;
 }
 
 // the most pictures a launch may hold, of pictures that take per_picture bytes of device memory each
@@ -674,8 +698,9 @@ void Engine::feeder()
                 continue;
             }
         }
-        if (cur && (!same_params(cur->params, p0) || !same_geometry(cur->geom, g0))) {   // a batch holds one set of stream
-            close_batch(cur);                                                              // parameters and one geometry
+        const mvhp_color_params_t c0 = picture_color(order_[first_seq], p0, g0);
+        if (cur && (!same_params(cur->params, p0) || !same_geometry(cur->geom, g0) || !same_color(cur->color, c0))) {   // a batch holds one
+            close_batch(cur);                                                // set of stream parameters, one geometry and one colour setting
             cur = nullptr;
         }
         const int avail = rg ? (int)(rg->seqs.size() - rg->pos) : std::min(allowance(), n_order_ - pos_);
@@ -685,6 +710,7 @@ void Engine::feeder()
             nb->params = p0;
             nb->geom = g0;
             nb->use_geom = use0;
+            nb->color = c0;
             nb->capacity = batch_capacity(p0, g0, use0, avail);
             nb->retry = rg != nullptr;
             nb->exclude_ctx = rg ? rg->exclude_ctx : -1;
@@ -704,6 +730,7 @@ void Engine::feeder()
             bool ui = false;
             std::string why;
             if (!picture_geometry(order_[seq_at(same)], pi, gi, ui, why) || !same_geometry(gi, g0)) break;
+            if (!same_color(picture_color(order_[seq_at(same)], pi, gi), c0)) break;
             same++;
         }
         n = same;
@@ -976,6 +1003,7 @@ void Engine::launcher(int k)
         else if (w_.png && !(api_.caps & CAP_PNG)) err = "this device table has no PNG operation";
         else if (b->use_geom && !w_.jpeg && !(api_.caps & CAP_GEOMETRY)) err = "this device table has no output-geometry operation";
         else if (w_.turns && !(api_.caps & CAP_ORIENT)) err = "this device table has no orientation operation";
+        else if (w_.color && !(api_.caps & CAP_COLOR)) err = "this device table has no colour operation";
         else {
             auto buf = [&](BufKind k) { return need(*b, k) ? b->buf->m[k].p : nullptr; };   // (a buffer may hold an earlier batch's kind)
             BatchJob job{};
@@ -986,7 +1014,8 @@ void Engine::launcher(int k)
             job.n = b->total;
             job.d_yuv = buf(kYuv);
             job.d_rgb = buf(kRgb);
-            job.geom = b->use_geom || w_.jpeg || w_.png ? &b->geom : nullptr;
+            job.geom = b->use_geom || w_.jpeg || w_.png || w_.color ? &b->geom : nullptr;
+            job.color = w_.color ? &b->color : nullptr;
             job.out_yuv = buf(kOutYuv);
             job.out_rgb = buf(kOutRgb);
             job.turns = w_.turns;
@@ -1221,8 +1250,9 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
                    mvhp_picture_sink_t sink, mvhp_picture_sink_ex_t sink_ex, void *user, mvhp_decode_stats_t *stats,
                    std::string &err)
 {
-    if (req && ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_SCORE | MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK)) || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2)))) {
-        err = "malformed output request (box sides must be at least 2)";
+    if (req && ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_SCORE | MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK | MVHP_OUTPUT_ASPECT | MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE_MASK)) ||
+                ((req->flags & MVHP_OUTPUT_COLOR_MODE_MASK) >> MVHP_OUTPUT_COLOR_MODE_SHIFT) > 4 || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2)))) {
+        err = "malformed output request (box sides must be at least 2, colour modes are 0 to 4)";
         return MVHP_FAILURE;
     }
     if ((out_mask & MVHP_OUT_JPEG) && sink) {
@@ -1255,6 +1285,10 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         req_ = req ? *req : mvhp_output_request_t{};
         w_.score = (req_.flags & MVHP_OUTPUT_SCORE) != 0;
         req_.flags &= ~MVHP_OUTPUT_SCORE;   // (what is left decides the geometry: none = the path of a call without a request)
+        // colour: only where the call delivers RGB or PNG; otherwise, and always for the geometry, the request without the bits
+        w_.color = (req_.flags & MVHP_OUTPUT_COLOR) != 0 && (w_.rgb || w_.png);
+        color_mode_ = (int)((req_.flags & MVHP_OUTPUT_COLOR_MODE_MASK) >> MVHP_OUTPUT_COLOR_MODE_SHIFT);
+        req_.flags &= ~(MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE_MASK);
         w_.turns = mvhp_output_turns(&s, &req_);
         if (w_.turns == 0) req_.flags &= ~(MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK);   // (turns that come to 0: today's paths exactly)
         stop_ = false; sink_waiting_ = false;

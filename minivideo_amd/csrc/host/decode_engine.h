@@ -44,6 +44,10 @@ struct BatchJob {
                                       // `geom` -- out_rgb where a pass behind the reconstruction wrote it, else the fused d_rgb --
                                       // into the same `blob` and `table`
     uint8_t *blob; size_t blob_cap; mvhp_jpeg_entry_t *table;
+    const mvhp_color_params_t *color;   // NULL: RGB by the reference's formula, fused or inside the passes.  Else no pass and no
+                                        // epilogue makes RGB: mvhp_color_dev of the FINAL planes -- out_yuv into out_rgb where a
+                                        // pass behind the reconstruction ran (both set), else d_yuv into d_rgb with `geom` the coded
+                                        // size -- and `png` reads that RGB.  Never beside `jpeg`
     mvhp_luma_stats_t *stats;   // NULL: no picture scores.  Else mvhp_luma_stats_dev over the crop rectangle of `geom` (the whole
                                 // picture without one) on the n coded planes in d_yuv -> n records
 };
@@ -53,7 +57,7 @@ struct BatchDone {
 };
 
 // what run_batch can do beyond pictures of the coded size; a job that needs a missing bit fails in the engine, with a message
-enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4, CAP_ORIENT = 8, CAP_PNG = 16 };
+enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4, CAP_ORIENT = 8, CAP_PNG = 16, CAP_COLOR = 32 };
 
 // Every operation blocks its calling thread until the device has finished it; the engine runs one thread per queue
 // and context, which is what overlaps upload(k+1), kernel(k) and download(k-1).  *ms = device-side duration.

@@ -223,6 +223,40 @@ bool effective_intra_scaling(const ScalingLists &sps, const ScalingLists &pps, b
     return nonflat;
 }
 
+// vui_parameters() (E.1.1) from aspect_ratio_info to chroma_loc_info, stopping before timing_info (no HRD).  The reference reads
+// the same fields and traces them (h264_parameterset.c:1318-1350).  A reader that reaches the RBSP's stop bit or a chroma_sample_loc_type
+// above 5 leaves every display field "unspecified"; the SPS itself is never touched.
+static void parse_vui_display(BitReader &br, Sps &s)
+{
+    static const uint8_t kSar[17][2] = {{0, 0}, {1, 1}, {12, 11}, {10, 11}, {16, 11}, {40, 33}, {24, 11}, {20, 11}, {32, 11},
+                                        {80, 33}, {18, 11}, {15, 11}, {64, 33}, {160, 99}, {4, 3}, {3, 2}, {2, 1}};   // Table E-1
+    uint32_t sw = 0, sh = 0, loc = 0;
+    bool signal = false, full = false;
+    int matrix = 2;
+    if (br.bit()) {   // aspect_ratio_info_present_flag
+        const uint32_t idc = br.bits(8);
+        if (idc == 255) { sw = br.bits(16); sh = br.bits(16); }
+        else if (idc <= 16) { sw = kSar[idc][0]; sh = kSar[idc][1]; }
+    }
+    if (br.bit()) br.bit();   // overscan_info_present_flag, overscan_appropriate_flag
+    signal = br.bit();        // video_signal_type_present_flag
+    if (signal) {
+        br.bits(3);           // video_format
+        full = br.bit();
+        if (br.bit()) { br.bits(8); br.bits(8); matrix = (int)br.bits(8); }   // colour_description: primaries, transfer, matrix
+    }
+    if (br.bit()) { loc = br.ue(); br.ue(); }   // chroma_loc_info: top field, bottom field
+    // (behind these fields a whole VUI has at least its five remaining flags: one that ends here, or in the stop bit, was cut off)
+    if (!br.more_rbsp_data() || loc > 5) return;
+    if (sw == 0 || sh == 0) sw = sh = 0;
+    // reduced by the greatest common divisor (Euclid; when the remainder reaches 0, `a` holds it)
+    for (uint32_t a = sw, b = sh; b != 0;) { const uint32_t t = a % b; a = b; b = t; if (b == 0) { sw /= a; sh /= a; } }
+    s.sar_w = sw; s.sar_h = sh;
+    s.signal_present = signal; s.full_range = full;
+    s.matrix_coefficients = matrix;
+    s.chroma_loc = (int)loc;
+}
+
 int parse_sps(BitReader &br, Sps &s, std::string &err, bool spec)
 {
     s = Sps();
@@ -277,12 +311,13 @@ int parse_sps(BitReader &br, Sps &s, std::string &err, bool spec)
     s.frame_cropping = br.bit();
     if (s.frame_cropping)
         for (int i = 0; i < 4; i++) s.crop[i] = (int)br.ue(); // parsed, never applied (export.c:80-81)
-    br.bit(); // vui_parameters_present_flag: VUI is parse-and-ignore in the reference; nothing after it matters
+    s.vui_present = br.bit(); // vui_parameters_present_flag: parse-and-ignore in the reference; nothing after it changes a picture
     if (br.overrun()) { err = "SPS: truncated"; return RC_FAILURE; }
     if (s.width_mbs <= 0 || s.height_map_units <= 0 || s.width_mbs > 1024 || s.height_map_units > 1024) {
         err = "SPS: picture size out of range";
         return RC_FAILURE;
     }
+    if (s.vui_present) parse_vui_display(br, s);   // (cannot fail the SPS)
     s.valid = true;
     return RC_SUCCESS;
 }

@@ -54,6 +54,13 @@ struct Sps {
     int      crop[4] = {0, 0, 0, 0};
     bool     qpprime_y_zero_transform_bypass = false;
     ScalingLists scaling;   // seq_scaling_matrix (only parsed for MVHP_STREAM_SPEC streams; the reference envelope has none)
+    // VUI (E.1.1), up to and excluding timing_info.  Information only (mvhp_stream_display): nothing decodes differently, and a
+    // VUI that ends early or holds a value out of range never fails the SPS -- these fields then keep their "unspecified" values
+    bool     vui_present = false;
+    uint32_t sar_w = 0, sar_h = 0;            // after Table E-1, reduced; 0:0 = unspecified
+    bool     signal_present = false, full_range = false;
+    int      matrix_coefficients = 2;         // 2 = unspecified (also when colour_description is absent)
+    int      chroma_loc = 0;                  // chroma_sample_loc_type_top_field; 0 when absent
 };
 
 struct Pps {

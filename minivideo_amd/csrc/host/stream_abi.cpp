@@ -240,6 +240,61 @@ MVHP_EXPORT int mvhp_stream_idr_count(const mvhp_stream_t *s) { return s ? (int)
 
 MVHP_EXPORT int mvhp_stream_rotation(const mvhp_stream_t *s) { return s ? 90 * (s->quarter_turns & 3) : 0; }
 
+MVHP_EXPORT int mvhp_stream_display(const mvhp_stream_t *s, int idr, mvhp_display_info_t *out)
+{
+    if (!s || !out || idr < 0 || (size_t)idr >= s->idrs.size() || !s->idrs[idr].ok) return MVHP_FAILURE;
+    const Sps &sps = s->idrs[idr].sps;
+    memset(out, 0, sizeof(*out));
+    out->sar_w = sps.sar_w;
+    out->sar_h = sps.sar_h;
+    out->vui_present = sps.vui_present;
+    out->signal_present = sps.signal_present;
+    out->full_range = sps.full_range;
+    out->matrix_coefficients = (uint32_t)sps.matrix_coefficients;
+    out->chroma_loc = (uint32_t)sps.chroma_loc;
+    return MVHP_SUCCESS;
+}
+
+// ---- colour parameters (host only; include/minivideo_hotpath.h "Colour conversion") ----
+
+// round(2^14 num / den), num and den positive
+static int32_t q14(__int128 num, __int128 den) { return (int32_t)((2 * num * 16384 + den) / (2 * den)); }
+
+MVHP_EXPORT int mvhp_color_coefficients(int matrix, int full_range, int32_t out[6])
+{
+    if (!out || (matrix != MVHP_MATRIX_BT601 && matrix != MVHP_MATRIX_BT709) || (full_range != 0 && full_range != 1)) return MVHP_FAILURE;
+    // Kr, Kb in ten-thousandths; Kg = 1 - Kr - Kb.  R = Y + 2 (1 - Kr) Cr, B = Y + 2 (1 - Kb) Cb,
+    // G = Y - 2 Kb (1 - Kb) / Kg Cb - 2 Kr (1 - Kr) / Kg Cr; limited range scales luma by 255/219 and chroma by 255/224
+    const int64_t D = 10000, kr = matrix == MVHP_MATRIX_BT709 ? 2126 : 2990, kb = matrix == MVHP_MATRIX_BT709 ? 722 : 1140;
+    const int64_t kg = D - kr - kb;
+    const int64_t ln = full_range ? 1 : 255, ld = full_range ? 1 : 219, cn = full_range ? 1 : 255, cd = full_range ? 1 : 224;
+    out[0] = q14(ln, ld);
+    out[1] = q14((__int128)2 * (D - kr) * cn, (__int128)D * cd);
+    out[2] = q14((__int128)2 * (D - kb) * cn, (__int128)D * cd);
+    out[3] = q14((__int128)2 * kb * (D - kb) * cn, (__int128)kg * D * cd);
+    out[4] = q14((__int128)2 * kr * (D - kr) * cn, (__int128)kg * D * cd);
+    out[5] = full_range ? 0 : 16;
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT int mvhp_color_resolve(const mvhp_display_info_t *d, uint32_t coded_w, uint32_t coded_h, int mode, mvhp_color_params_t *out)
+{
+    if (!out || mode < 0 || mode > 4) return MVHP_FAILURE;
+    memset(out, 0, sizeof(*out));
+    if (mode == 0) {
+        const uint32_t mc = d ? d->matrix_coefficients : 2u;
+        if (mc == 1) out->matrix = MVHP_MATRIX_BT709;
+        else if (mc == 5 || mc == 6) out->matrix = MVHP_MATRIX_BT601;
+        else out->matrix = (coded_w >= 1280 || coded_h > 576) ? MVHP_MATRIX_BT709 : MVHP_MATRIX_BT601;   // unspecified or unsupported
+        out->full_range = d && d->signal_present && d->full_range;
+    } else {
+        out->matrix = (mode == 2 || mode == 4) ? MVHP_MATRIX_BT709 : MVHP_MATRIX_BT601;
+        out->full_range = mode >= 3;
+    }
+    out->siting = (d && (d->chroma_loc & 1)) ? MVHP_CHROMA_CENTER : MVHP_CHROMA_LEFT;
+    return MVHP_SUCCESS;
+}
+
 MVHP_EXPORT int mvhp_stream_params(const mvhp_stream_t *s, int idr, mvhp_stream_params_t *out)
 {
     if (!s || !out || idr < 0 || (size_t)idr >= s->idrs.size() || !s->idrs[idr].ok) return MVHP_FAILURE;
@@ -297,6 +352,15 @@ MVHP_EXPORT int mvhp_geometry_fit(uint32_t cw, uint32_t ch, uint32_t bw, uint32_
     return MVHP_SUCCESS;
 }
 
+MVHP_EXPORT int mvhp_geometry_aspect(uint32_t cw, uint32_t ch, uint32_t sar_w, uint32_t sar_h, uint32_t *ow, uint32_t *oh)
+{
+    uint32_t w = 0, h = 0;
+    if (!ow || !oh || (cw & 1) || (ch & 1) || !mvrs::aspect(cw, ch, sar_w, sar_h, w, h)) return MVHP_FAILURE;
+    *ow = w;
+    *oh = h;
+    return MVHP_SUCCESS;
+}
+
 MVHP_EXPORT int mvhp_output_turns(const mvhp_stream_t *s, const mvhp_output_request_t *req)
 {
     if (!req) return 0;
@@ -311,6 +375,11 @@ MVHP_EXPORT int mvhp_output_geometry(const mvhp_stream_t *s, int idr, const mvhp
     const int turns = mvhp_output_turns(s, req_in);
     mvhp_output_request_t unturned;
     const mvhp_output_request_t *req = req_in;
+    if (req_in && (req_in->flags & (MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE_MASK))) {   // colour changes no geometry
+        mvhp_output_request_t plain = *req_in;
+        plain.flags &= ~(MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE_MASK);
+        return mvhp_output_geometry(s, idr, &plain, out);
+    }
     if (req_in && (req_in->flags & (MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK))) {
         unturned = *req_in;
         unturned.flags &= ~(MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK);
@@ -333,12 +402,19 @@ MVHP_EXPORT int mvhp_output_geometry(const mvhp_stream_t *s, int idr, const mvhp
         out->crop_h = out->out_h = p.height_mbs * 16;
         return MVHP_SUCCESS;
     }
-    if ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX)) || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2))) {
+    if ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_ASPECT)) || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2))) {
         g_stream_err = "mvhp_output_geometry: malformed request (box sides must be at least 2)";
         return MVHP_FAILURE;
     }
     if (mvhp_stream_crop(s, idr, out) != MVHP_SUCCESS) return MVHP_FAILURE;
-    if (req->flags & MVHP_OUTPUT_BOX) mvrs::fit(out->crop_w, out->crop_h, req->box_w, req->box_h, out->out_w, out->out_h);
+    if (req->flags & MVHP_OUTPUT_ASPECT) {   // square samples first: one axis of the crop shrinks; the box is fitted to that size
+        const Sps &sps = s->idrs[idr].sps;
+        mvrs::aspect(out->crop_w, out->crop_h, sps.sar_w, sps.sar_h, out->out_w, out->out_h);
+    }
+    if (req->flags & MVHP_OUTPUT_BOX) {
+        const uint32_t dw = out->out_w, dh = out->out_h;
+        mvrs::fit(dw, dh, req->box_w, req->box_h, out->out_w, out->out_h);
+    }
     return MVHP_SUCCESS;
 }
 

@@ -39,6 +39,9 @@ def lib():
                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.mvgen_stream_crop.restype = C.c_size_t
         L.mvgen_stream_crop.argtypes = [C.POINTER(GenCfg), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mvgen_stream_vui.restype = C.c_size_t
+        L.mvgen_stream_vui.argtypes = [C.POINTER(GenCfg), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -61,6 +64,59 @@ def make_stream_crop(width_mbs, height_mbs, n_frames, crops, seed=1, profile="ba
         raise ValueError("generator rejected the configuration")
     out = np.zeros(n, np.uint8)
     assert L.mvgen_stream_crop(C.byref(cfg), cr.shape[0], cr.ctypes.data, out.ctypes.data, n, packed.ctypes.data) == n
+    return out, packed
+
+
+def vui_record(sar=None, overscan=None, full_range=None, matrix=None, chroma_loc=None, timing=False, video_format=5,
+               primaries=2, transfer=2):
+    """One VUI record for make_stream_vui.  sar: None (no aspect_ratio_info), an aspect_ratio_idc, or (w, h) = idc 255 with that
+    extended pair; overscan: None or the overscan_appropriate_flag; full_range / matrix: None leaves the syntax out (a matrix
+    alone writes video_signal_type with video_full_range_flag 0); chroma_loc: None, a type for both fields or (top, bottom);
+    timing: a timing_info tail behind the fields the front end reads."""
+    r = [0] * 16
+    if sar is not None:
+        r[0] = 1
+        if isinstance(sar, tuple):
+            r[1], r[2], r[3] = 255, int(sar[0]), int(sar[1])
+        else:
+            r[1] = int(sar)
+    if overscan is not None:
+        r[4] = 2 if overscan else 1
+    if full_range is not None or matrix is not None:
+        r[5], r[6], r[7] = 1, int(video_format), int(bool(full_range))
+        if matrix is not None:
+            r[8], r[9], r[10], r[11] = 1, int(primaries), int(transfer), int(matrix)
+    if chroma_loc is not None:
+        top, bottom = chroma_loc if isinstance(chroma_loc, tuple) else (chroma_loc, chroma_loc)
+        r[12], r[13], r[14] = 1, int(top), int(bottom)
+    r[15] = int(bool(timing))
+    return r
+
+
+def make_stream_vui(width_mbs, height_mbs, n_frames, vuis, keep_bits=-1, crops=None, seed=1, profile="baseline", dense=True,
+                    cqp_offsets=(0, 0), sps_pps_every_frame=False, qp_range=(24, 32), max_level=32, allow_qp36_i16=False):
+    """make_stream with a VUI in every SPS: `vuis` is a list of vui_record()s; SPS k of the stream (one per picture with
+    sps_pps_every_frame) carries vuis[k % len(vuis)] and, with `crops` (as make_stream_crop), crops[k % len(crops)].
+    keep_bits >= 0 cuts every SPS off after that many bits of its VUI.  The macroblocks are those of make_stream with the same
+    arguments.  Returns (stream, packed[n, W*H, 800])."""
+    prof = {"baseline": (66, 0, 0), "main": (77, 1, 0), "main_cavlc": (77, 0, 0), "high": (100, 1, 1),
+            "high_cavlc": (100, 0, 1), "high_4x4": (100, 1, 0)}[profile]
+    cfg = GenCfg(width_mbs, height_mbs, n_frames, seed, prof[0], prof[1], prof[2], 1 if dense else 0,
+                 cqp_offsets[0], cqp_offsets[1], int(sps_pps_every_frame), int(allow_qp36_i16),
+                 qp_range[0], qp_range[1], max_level)
+    L = lib()
+    vr = np.ascontiguousarray(np.array(vuis, np.int32).reshape(-1, 16))
+    cr = np.ascontiguousarray(np.array(crops if crops else [], np.int32).reshape(-1, 4))
+    packed = np.zeros((n_frames, width_mbs * height_mbs, 800), np.uint8)
+
+    def call(out, cap):
+        return L.mvgen_stream_vui(C.byref(cfg), vr.shape[0], vr.ctypes.data, int(keep_bits), cr.shape[0],
+                                  cr.ctypes.data if cr.shape[0] else None, out, cap, packed.ctypes.data)
+    n = call(None, 0)
+    if n == 0:
+        raise ValueError("generator rejected the configuration")
+    out = np.zeros(n, np.uint8)
+    assert call(out.ctypes.data, n) == n
     return out, packed
 
 

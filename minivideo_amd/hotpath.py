@@ -58,6 +58,10 @@ OUT_JPEG = 4                                                            # mvhp_e
 OUT_PNG = 8                                                             # ... (MVHP_OUT_PNG)
 OUTPUT_CROP, OUTPUT_BOX, OUTPUT_SCORE = 1, 2, 4                          # mvhp_output_request_t flags (MVHP_OUTPUT_*)
 OUTPUT_ORIENT, OUTPUT_ROTATE_SHIFT = 8, 4                                # ... the stream's own rotation; bits 4-5: further turns
+OUTPUT_ASPECT, OUTPUT_COLOR, OUTPUT_COLOR_MODE_SHIFT = 0x800, 0x80, 8     # ... square samples; RGB by a colour pass, bits 8-10: its mode
+MATRIX_BT601, MATRIX_BT709 = 0, 1                                       # mvhp_color_params_t::matrix (MVHP_MATRIX_*)
+CHROMA_NEAREST, CHROMA_LEFT, CHROMA_CENTER = 0, 1, 2                    # mvhp_color_params_t::siting (MVHP_CHROMA_*)
+COLOR_MODES = ("auto", "bt601", "bt709", "bt601-full", "bt709-full")    # MVHP_OUTPUT_COLOR_MODE(index); MINIVIDEO_COLOR's values
 ORIENT_SRC_CODED = 1                                                    # mvhp_orient_dev src_flags (MVHP_ORIENT_SRC_CODED)
 
 
@@ -99,12 +103,23 @@ class OutputRequest(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("box_w", C.c_uint32), ("box_h", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-def output_request(output, rotate=None):
+def color_flags(color):
+    """None -> 0; one of COLOR_MODES -> MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE(its index)"""
+    if color is None:
+        return 0
+    if color not in COLOR_MODES:
+        raise ValueError("color must be one of " + ", ".join(COLOR_MODES))
+    return OUTPUT_COLOR | (COLOR_MODES.index(color) << OUTPUT_COLOR_MODE_SHIFT)
+
+
+def output_request(output, rotate=None, aspect=False, color=None):
     """None -> None (the coded size); "crop" -> the SPS crop; (w, h) -> the crop fitted into a w x h box.  rotate (see
-    rotate_flags()) adds the orientation bits; with rotate given the result is never None"""
-    rot = rotate_flags(rotate)
+    rotate_flags()) adds the orientation bits; with rotate given the result is never None.  aspect=True adds
+    MVHP_OUTPUT_ASPECT (square samples; implies the crop), color (see color_flags()) the colour bits; with either the result is
+    never None"""
+    rot = rotate_flags(rotate) | (OUTPUT_ASPECT if aspect else 0) | color_flags(color)
     if output is None:
-        return OutputRequest(rot, 0, 0, 0) if rotate is not None else None
+        return OutputRequest(rot, 0, 0, 0) if (rotate is not None or aspect or color is not None) else None
     if output == "crop":
         return OutputRequest(OUTPUT_CROP | rot, 0, 0, 0)
     w, h = output
@@ -219,10 +234,60 @@ def output_turns(stream_handle, output=None, rotate=None):
     return int(lib().mvhp_output_turns(stream_handle, C.byref(req) if req is not None else None))
 
 
-def output_geometry(stream_handle, idr, output, rotate=None):
-    """mvhp_output_geometry under output_request(output, rotate), or None: what the sink gets"""
+class DisplayInfo(C.Structure):
+    """mvhp_display_info_t: what the VUI of a picture's SPS says about display"""
+    _fields_ = [("sar_w", C.c_uint32), ("sar_h", C.c_uint32), ("vui_present", C.c_uint32), ("signal_present", C.c_uint32),
+                ("full_range", C.c_uint32), ("matrix_coefficients", C.c_uint32), ("chroma_loc", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class ColorParams(C.Structure):
+    """mvhp_color_params_t"""
+    _fields_ = [("matrix", C.c_int32), ("full_range", C.c_int32), ("siting", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_tuple(self):
+        return int(self.matrix), int(self.full_range), int(self.siting)
+
+
+def stream_display(stream_handle, idr):
+    """mvhp_stream_display: DisplayInfo of picture `idr` (sample aspect ratio, range, matrix, chroma location), or None"""
+    d = DisplayInfo()
+    return d if lib().mvhp_stream_display(stream_handle, int(idr), C.byref(d)) == SUCCESS else None
+
+
+def color_coefficients(matrix, full_range):
+    """mvhp_color_coefficients: (cy, crv, cbu, gcb, gcr, yoff), or None for values the header does not name (no device needed)"""
+    out = (C.c_int32 * 6)()
+    if lib().mvhp_color_coefficients(int(matrix), int(full_range), out) != SUCCESS:
+        return None
+    return tuple(int(x) for x in out)
+
+
+def color_resolve(display, coded_w, coded_h, mode=0):
+    """mvhp_color_resolve: ColorParams for pictures of coded_w x coded_h whose stream says `display` (a DisplayInfo or None) under
+    `mode` (0 .. 4 or one of COLOR_MODES), or None for a mode outside them (no device needed)"""
+    if isinstance(mode, str):
+        mode = COLOR_MODES.index(mode)
+    out = ColorParams()
+    rc = lib().mvhp_color_resolve(C.byref(display) if display is not None else None, int(coded_w), int(coded_h), int(mode), C.byref(out))
+    return out if rc == SUCCESS else None
+
+
+def geometry_aspect(cw, ch, sar_w, sar_h):
+    """the aspect rule (mvhp_geometry_aspect): (out_w, out_h), or None for malformed arguments"""
+    ow, oh = C.c_uint32(), C.c_uint32()
+    if lib().mvhp_geometry_aspect(cw, ch, sar_w, sar_h, C.byref(ow), C.byref(oh)) != SUCCESS:
+        return None
+    return ow.value, oh.value
+
+
+def output_geometry(stream_handle, idr, output, rotate=None, aspect=False):
+    """mvhp_output_geometry under output_request(output, rotate, aspect), or None: what the sink gets"""
     g = OutputGeometry()
-    req = output_request(output, rotate)
+    req = output_request(output, rotate, aspect)
     rc = lib().mvhp_output_geometry(stream_handle, int(idr), C.byref(req) if req is not None else None, C.byref(g))
     return g if rc == SUCCESS else None
 
@@ -310,6 +375,16 @@ def lib():
     L.mvhp_resample_dev.argtypes = [vp, pp, pg, vp, i32, vp, vp, vp]
     L.mvhp_orient_dev.restype = i32
     L.mvhp_orient_dev.argtypes = [vp, pp, pg, i32, u32, vp, i32, vp, vp, vp]
+    L.mvhp_stream_display.restype = i32
+    L.mvhp_stream_display.argtypes = [vp, i32, C.POINTER(DisplayInfo)]
+    L.mvhp_geometry_aspect.restype = i32
+    L.mvhp_geometry_aspect.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
+    L.mvhp_color_coefficients.restype = i32
+    L.mvhp_color_coefficients.argtypes = [i32, i32, C.POINTER(C.c_int32)]
+    L.mvhp_color_resolve.restype = i32
+    L.mvhp_color_resolve.argtypes = [C.POINTER(DisplayInfo), u32, u32, i32, C.POINTER(ColorParams)]
+    L.mvhp_color_dev.restype = i32
+    L.mvhp_color_dev.argtypes = [vp, pg, C.POINTER(ColorParams), vp, i32, vp, vp]
     L.mvhp_stream_rotation.restype = i32
     L.mvhp_stream_rotation.argtypes = [vp]
     L.mvhp_output_turns.restype = i32
@@ -448,6 +523,15 @@ class HotPath:
                                      ORIENT_SRC_CODED if coded else 0, d_src, int(n), d_yuv_out, d_rgb_out, stream)
         if rc != SUCCESS:
             raise _err(self._L, "mvhp_orient_dev")
+
+    def color_dev(self, geom, color, d_yuv, n, d_rgb_out, stream=None):
+        """n dense planar pictures of geom.out_w x geom.out_h (device) -> n RGB pictures (device) by `color`, a ColorParams or a
+        (matrix, full_range, siting) triple.  Asynchronous."""
+        if not isinstance(color, ColorParams):
+            color = ColorParams(int(color[0]), int(color[1]), int(color[2]), 0)
+        rc = self._L.mvhp_color_dev(self._h, C.byref(geom), C.byref(color), d_yuv, int(n), d_rgb_out, stream)
+        if rc != SUCCESS:
+            raise _err(self._L, "mvhp_color_dev")
 
     def luma_stats_dev(self, params, geom, d_yuv_coded, n, d_stats, stream=None):
         """n coded pictures (device) -> n LumaStats records (LUMA_STATS_DTYPE, device) over geom's crop rectangle.  Asynchronous."""
@@ -628,7 +712,7 @@ class Engine:
         self._L.mvhp_engine_release_picture(self._h, int(seq))
 
     def decode(self, stream_handle, order, wanted=None, want_rgb=False, sink=None, output=None, jpeg=None, restart_mcus=0,
-               score=False, rotate=None, png=False):
+               score=False, rotate=None, png=False, aspect=False, color=None):
         """sink(seq, idr, rc, err, params, yuv ndarray | None, rgb ndarray | None) -> 1 accept / 0 reject / -1 stop /
         2 accept and keep until release_picture(seq); the arrays are views of page-locked memory valid only during the call
         (or until the release).  Returns (rc, stats dict).
@@ -643,14 +727,17 @@ class Engine:
         score=True: MVHP_OUTPUT_SCORE -- the sink is called as for `output` (with the geometry, also for pictures of the coded
         size) and finds each picture's score in geometry.score; the pictures are the same bytes.
         rotate = "auto" (the stream's own rotation, stream_rotation()) or 0 / 90 / 180 / 270 (clockwise): the pictures are
-        turned on the device; the sink is called as for `output`, and its geometry is the one of the turned picture."""
+        turned on the device; the sink is called as for `output`, and its geometry is the one of the turned picture.
+        aspect=True: MVHP_OUTPUT_ASPECT -- the stream's sample aspect ratio is applied (square samples out); implies the crop.
+        color = "auto" or "bt601" / "bt709" / "bt601-full" / "bt709-full": MVHP_OUTPUT_COLOR -- the RGB (and the PNG files) are
+        made from the final planes by the stream's own matrix, range and chroma siting, or by the forced matrix and range."""
         order = (C.c_int * len(order))(*order)
         st = DecodeStats()
         n_wanted = len(order) if wanted is None else wanted
         if png and jpeg is not None:
             raise ValueError("png and jpeg are two output kinds: a call delivers one")
-        if output is not None or jpeg is not None or score or rotate is not None or png:
-            req = output_request(output, rotate) or OutputRequest(0, 0, 0, 0)
+        if output is not None or jpeg is not None or score or rotate is not None or png or aspect or color is not None:
+            req = output_request(output, rotate, aspect, color) or OutputRequest(0, 0, 0, 0)
             if score:
                 req.flags |= OUTPUT_SCORE
             if jpeg is not None:

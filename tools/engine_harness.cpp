@@ -4,11 +4,13 @@
 // lets the sink check that the right picture arrives in the right place, in order, through chunks, batches, several
 // contexts and a re-queue.  Nothing here is part of libminivideo.so.
 //
-// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes> [jpeg | png | score | orient]]]
+// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes> [jpeg | png | score | orient | color <stream whose SPS VUI changes>]]]
 // The fourth argument adds the geometry mode: mvhp_engine_decode_ex and minivideo_decode under MINIVIDEO_CROP /
 // MINIVIDEO_THUMBNAIL against the stub's resample targets.  A fifth argument adds the JPEG mode (MVHP_OUT_JPEG), the PNG mode (MVHP_OUT_PNG against the stub's PNG operation) or the
 // score mode (MVHP_OUTPUT_SCORE against the stub's picture scores, which sum the stub's coded planes on the CPU), or the orient
-// mode (MVHP_OUTPUT_ORIENT / MVHP_OUTPUT_ROTATE and MINIVIDEO_ROTATE against the stub's turn).
+// mode (MVHP_OUTPUT_ORIENT / MVHP_OUTPUT_ROTATE and MINIVIDEO_ROTATE against the stub's turn), or the color mode (MVHP_OUTPUT_ASPECT /
+// MVHP_OUTPUT_COLOR, MINIVIDEO_ASPECT and MINIVIDEO_COLOR against the stub's colour pass; a sixth argument names a stream whose
+// SPSs alternate between two VUIs that differ in matrix and range only, so that the colour setting changes and no geometry does).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -137,13 +139,17 @@ mvhp_luma_stats_t expected_stats(uint64_t h, bool pattern, const mvhp_stream_par
 // * turns (orient mode): the outputs are stamped as resample targets are -- `geom` is the delivered geometry, so the output buffers
 //   must hold n pictures of it -- and a batch that scales before the turn must bring the buffer of the unturned planes, which is
 //   written in full, and no other batch may bring one;
+// * colour (color mode): no other pass may have been asked for RGB; the RGB -- out_rgb behind a pass, where the planes out_yuv must
+//   be there to read, else d_rgb of the coded size -- is stamped as above, with the setting in byte 16 (0xc0 | matrix << 3 |
+//   full_range << 2 | siting) and 0x7b last; planes of the coded size stay the output they are without the pass;
 // * scores: honest sums over the rectangle of the coded planes the batch buffer holds.
 // * PNG: the RGB the encoder reads is stamped as above (the fused RGB of a batch of the coded size, the resample or turn target
 //   otherwise; no output planes), and every picture gets a "file" of 64 + checksum % (the longest file - 64) bytes of 0x3d that
 //   starts with bytes 8-15 of that RGB (the checksum) and ends in 0x7a; the blob must be n x the longest file rounded to 16, so
 //   no picture is too big.
-constexpr uint8_t kLastYuv = 0x77, kLastRgb = 0x78, kLastJpeg = 0x79, kLastPng = 0x7a;
-std::atomic<int> g_jpeg_calls{0}, g_stats_calls{0}, g_orient_calls{0}, g_mid_calls{0}, g_png_calls{0};
+constexpr uint8_t kLastYuv = 0x77, kLastRgb = 0x78, kLastJpeg = 0x79, kLastPng = 0x7a, kLastColor = 0x7b;
+std::atomic<int> g_jpeg_calls{0}, g_stats_calls{0}, g_orient_calls{0}, g_mid_calls{0}, g_png_calls{0}, g_color_calls{0};
+uint8_t color_tag(const mvhp_color_params_t &c) { return (uint8_t)(0xc0 | (c.matrix << 3) | (c.full_range << 2) | c.siting); }
 size_t stub_png_room(const mvhp_output_geometry_t *g) { return (mvhp::png_max_bytes((int)g->out_w, (int)g->out_h) + 15) & ~(size_t)15; }
 size_t stub_png_length(uint64_t h, const mvhp_output_geometry_t *g) { return 64 + (size_t)(h % (mvhp::png_max_bytes((int)g->out_w, (int)g->out_h) - 64)); }
 size_t stub_jpeg_length(uint64_t h, size_t raw) { return 32 + (size_t)(h % (raw / 2)); }
@@ -154,7 +160,16 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
     const mvhp_output_geometry_t *g = j.geom;
     const bool resample = j.out_yuv || j.out_rgb;
     (j.jpeg ? g_jpeg_calls : j.png ? g_png_calls : resample ? g_geometry_calls : g_recon_calls)++;
-    if (!j.d_yuv || (!j.jpeg && !j.png && (g != nullptr) != resample)) { err = "stub: geometry launch without buffers"; return MVHP_FAILURE; }
+    if (!j.d_yuv || (!j.jpeg && !j.png && !j.color && (g != nullptr) != resample)) { err = "stub: geometry launch without buffers"; return MVHP_FAILURE; }
+    if (j.color) {
+        if (!g || j.jpeg || (resample ? (!j.out_yuv || !j.out_rgb) : !j.d_rgb) || j.color->reserved || j.color->matrix < 0 || j.color->matrix > 1 ||
+            j.color->full_range < 0 || j.color->full_range > 1 || j.color->siting < 1 || j.color->siting > 2) {
+            err = "stub: colour pass without buffers or parameters";
+            return MVHP_FAILURE;
+        }
+        g_color_calls++;
+    }
+    const bool coded_out = !g || (j.color && !resample && !j.png);   // the planes of the coded size are what is delivered
     if (j.turns < 0 || j.turns > 3 || (!j.turns && j.mid_yuv) || (j.turns && (!g || !resample))) { err = "stub: orientation without buffers"; return MVHP_FAILURE; }
     if (j.turns) {
         const uint32_t w0 = (j.turns & 1) ? g->out_h : g->out_w, h0 = (j.turns & 1) ? g->out_w : g->out_h;   // before the turn
@@ -169,7 +184,7 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
         return MVHP_FAILURE;
     }
     // (PNG: RGB present -- fused where the pictures are of the coded size, a pass's target exactly where they are not -- no planes)
-    if (j.png && (!g || j.jpeg || !j.blob || !j.table || j.out_yuv || j.png->reserved || !(resample ? j.out_rgb : j.d_rgb) ||
+    if (j.png && (!g || j.jpeg || !j.blob || !j.table || (j.out_yuv && !j.color) || j.png->reserved || !(resample ? j.out_rgb : j.d_rgb) ||
                   (j.out_rgb != nullptr) != (j.turns != 0 || g->out_w != p->width_mbs * 16 || g->out_h != p->height_mbs * 16))) {
         err = "stub: PNG launch without buffers or parameters";
         return MVHP_FAILURE;
@@ -192,12 +207,12 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
     for (int i = 0; i < n; i++) {
         const uint64_t h = checksum((const uint8_t *)j.d_packed + (size_t)i * pb, pb);
         uint8_t *coded = j.d_yuv + (size_t)i * yb;
-        if (g) fill_coded(coded, yb, h);
+        if (!coded_out) fill_coded(coded, yb, h);
         else {
             memset(coded, 0x5a, yb);
             memcpy(coded, &h, sizeof(h));
         }
-        if (j.d_rgb && (!g || j.png)) {
+        if (j.d_rgb && (!g || j.png || (j.color && !resample))) {
             memset(j.d_rgb + (size_t)i * rb, 0xa5, rb);
             memcpy(j.d_rgb + (size_t)i * rb + 8, &h, sizeof(h));
         }
@@ -210,6 +225,11 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
             memset(j.out_rgb + (size_t)i * gr, 0xa5, gr);
             memcpy(j.out_rgb + (size_t)i * gr + 8, &h, sizeof(h));
             j.out_rgb[(size_t)i * gr + gr - 1] = kLastRgb;
+        }
+        if (j.color) {
+            uint8_t *rgb = resample ? j.out_rgb + (size_t)i * gr : j.d_rgb + (size_t)i * rb;
+            rgb[16] = color_tag(*j.color);
+            rgb[(resample ? gr : rb) - 1] = kLastColor;
         }
         if (j.jpeg) {
             const size_t len = stub_jpeg_length(h, gy);
@@ -256,7 +276,7 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
 
 mvengine::DeviceApi g_stub = {stub_device_count, stub_host_alloc, stub_host_free, stub_ctx_create, stub_ctx_destroy,
                                     stub_dev_alloc, stub_dev_free, stub_dev_free_bytes, stub_copy_n, stub_copy_n, stub_run_batch,
-                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_PNG,
+                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_PNG | mvengine::CAP_COLOR,
                                     nullptr, nullptr};   // (no placed arena on the stub device)
 
 uint64_t picture_checksum(const mvhp_stream &s, int idr)
@@ -354,6 +374,78 @@ struct CheckO {
             if (!rgb) { c.bad++; return 0; }
             memcpy(&got, rgb + 8, 8);
             if (got != h || rgb[0] != 0xa5 || rgb[gr - 1] != (coded ? 0xa5 : kLastRgb)) c.bad++;
+            c.bytes += gr;
+        } else if (rgb) c.bad++;
+        c.ok++;
+        return 1;
+    }
+};
+
+// sink of the color mode: the geometry mvhp_output_geometry announces, buffers sized by it; with the colour flag in a call that
+// delivers RGB the picture's RGB carries ITS OWN setting (mvhp_color_resolve of its display info under the request's mode, centred
+// where the pass scaled) and the colour pass's end mark, the planes are what they are without the flag
+struct CheckC {
+    const mvhp_stream *s = nullptr;
+    mvhp_output_request_t req{};
+    bool want_yuv = true, want_rgb = false, png = false;
+    int calls = 0, ok = 0, failed = 0, bad = 0, next_seq = 0, no_op = 0, settings_seen[16] = {0};
+    uint64_t bytes = 0;
+    std::vector<int> order;
+    static uint8_t expected_tag(const mvhp_stream *s, int idr, const mvhp_output_request_t &req, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g)
+    {
+        mvhp_display_info_t d;
+        mvhp_color_params_t c;
+        const bool have = mvhp_stream_display(s, idr, &d) == MVHP_SUCCESS;
+        mvhp_color_resolve(have ? &d : nullptr, p->width_mbs * 16, p->height_mbs * 16, (int)((req.flags & MVHP_OUTPUT_COLOR_MODE_MASK) >> MVHP_OUTPUT_COLOR_MODE_SHIFT), &c);
+        const int turns = mvhp_output_turns(s, &req);
+        const uint32_t w0 = (turns & 1) ? g->out_h : g->out_w, h0 = (turns & 1) ? g->out_w : g->out_h;
+        if (w0 != g->crop_w || h0 != g->crop_h) c.siting = MVHP_CHROMA_CENTER;
+        return color_tag(c);
+    }
+    static int sink(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                    const uint8_t *yuv, const uint8_t *rgb)
+    {
+        CheckC &c = *static_cast<CheckC *>(user);
+        c.calls++;
+        if (seq != c.next_seq || idr != c.order[(size_t)seq] || !g) c.bad++;
+        c.next_seq = seq + 1;
+        mvhp_output_geometry_t want;
+        const bool formed = mvhp_output_geometry(c.s, idr, &c.req, &want) == MVHP_SUCCESS;
+        if (rc != MVHP_SUCCESS) {
+            c.failed++;
+            if (err && strstr(err, "no colour operation")) c.no_op++;
+            else if (!err || !*err || yuv || rgb || formed) c.bad++;
+            return 0;
+        }
+        if (!formed || !g || want.crop_x != g->crop_x || want.crop_y != g->crop_y || want.crop_w != g->crop_w || want.crop_h != g->crop_h ||
+            want.out_w != g->out_w || want.out_h != g->out_h) { c.bad++; return 0; }
+        const int turns = mvhp_output_turns(c.s, &c.req);
+        const bool coded = turns == 0 && g->crop_x == 0 && g->crop_y == 0 && g->out_w == p->width_mbs * 16 && g->out_h == p->height_mbs * 16 &&
+                           g->crop_w == g->out_w && g->crop_h == g->out_h;
+        const bool color = (c.req.flags & MVHP_OUTPUT_COLOR) != 0;
+        const uint64_t h = picture_checksum(*c.s, idr);
+        const size_t gy = mvhp_geometry_yuv_bytes(g), gr = mvhp_geometry_rgb_bytes(g);
+        uint64_t got = 0;
+        if (c.png) {   // the stub's file starts with bytes 8-15 of the RGB it was made of; its length is in reserved[0]
+            if (yuv || !rgb || g->reserved[0] < 64) { c.bad++; return 0; }
+            memcpy(&got, rgb, 8);
+            if (got != h || rgb[g->reserved[0] - 1] != kLastPng) c.bad++;
+            c.bytes += 16 + g->reserved[0];
+            c.ok++;
+            return 1;
+        }
+        if (c.want_yuv) {
+            if (!yuv) { c.bad++; return 0; }
+            memcpy(&got, yuv, 8);
+            if (got != h || yuv[8] != 0x5a || yuv[gy - 1] != (coded ? 0x5a : kLastYuv)) c.bad++;
+            c.bytes += gy;
+        } else if (yuv) c.bad++;
+        if (c.want_rgb) {
+            if (!rgb) { c.bad++; return 0; }
+            memcpy(&got, rgb + 8, 8);
+            const uint8_t tag = color ? expected_tag(c.s, idr, c.req, p, g) : 0xa5;
+            if (got != h || rgb[0] != 0xa5 || rgb[16] != tag || rgb[gr - 1] != (color ? kLastColor : coded ? 0xa5 : kLastRgb)) c.bad++;
+            if (color) c.settings_seen[tag & 15]++;
             c.bytes += gr;
         } else if (rgb) c.bad++;
         c.ok++;
@@ -1336,6 +1428,215 @@ int main(int argc, char **argv)
                 rmdir(dir);
             }
             printf("ORIENT MODE DONE\n");
+        }
+        if (argc > 6 && !strcmp(argv[5], "color")) {   // ---- color mode: MVHP_OUTPUT_ASPECT / MVHP_OUTPUT_COLOR against the stub's colour pass ----
+            std::vector<uint8_t> b4 = read_file(argv[6]);
+            mvhp_stream s4;   // every SPS carries SAR 4:3 and a crop; even SPSs say BT.709 full range, odd ones BT.601 limited
+            s4.data = b4.data();
+            s4.size = b4.size();
+            EXPECT(s4.build(err) == h264::RC_SUCCESS);
+            const int n4 = (int)s4.idrs.size();
+            EXPECT(n4 >= 6);
+            std::vector<int> o4((size_t)n4);
+            for (int i = 0; i < n4; i++) o4[(size_t)i] = i;
+            auto run_c = [&](const char *name, mvhp_engine_opts_t o, const mvhp_stream &st, const std::vector<int> &order, int mask,
+                             const mvhp_output_request_t &req, CheckC &c, mvhp_decode_stats_t &stats) {
+                mvhp_engine_t *e = nullptr;
+                if (mvhp_engine_create(&o, &e) != MVHP_SUCCESS) { failures++; return MVHP_FAILURE; }
+                c.s = &st; c.req = req; c.order = order;
+                c.png = mask == MVHP_OUT_PNG;
+                c.want_rgb = !c.png && (mask & 1) != 0;
+                c.want_yuv = !c.png && (!c.want_rgb || (mask & 2) == 0);
+                const int rc = mvhp_engine_decode_ex(e, &st, order.data(), (int)order.size(), (int)order.size(), mask, &req, CheckC::sink, &c, &stats);
+                mvhp_engine_destroy(e);
+                printf("%-28s flags=%#x kind=%d rc=%d ok=%u failed=%u batches=%u geometry=%u d2h=%llu\n", name, req.flags, mask, rc, stats.pictures_ok,
+                       stats.pictures_failed, stats.batches, stats.geometry_launches, (unsigned long long)stats.d2h_bytes);
+                return rc;
+            };
+            {   // the display information and the aspect rule behind the geometry
+                mvhp_display_info_t d0, d1;
+                EXPECT(mvhp_stream_display(&s4, 0, &d0) == MVHP_SUCCESS && mvhp_stream_display(&s4, 1, &d1) == MVHP_SUCCESS);
+                EXPECT(d0.sar_w == 4 && d0.sar_h == 3 && d1.sar_w == 4 && d1.sar_h == 3 && d0.matrix_coefficients == 1 && d0.full_range == 1 &&
+                       d1.matrix_coefficients == 6 && d1.full_range == 0);
+                mvhp_output_geometry_t gc, ga, gb;
+                const mvhp_output_request_t rc_{MVHP_OUTPUT_CROP, 0, 0, 0}, ra{MVHP_OUTPUT_ASPECT, 0, 0, 0}, rb{MVHP_OUTPUT_ASPECT | MVHP_OUTPUT_BOX, 40, 40, 0};
+                EXPECT(mvhp_output_geometry(&s4, 0, &rc_, &gc) == MVHP_SUCCESS && mvhp_output_geometry(&s4, 0, &ra, &ga) == MVHP_SUCCESS &&
+                       mvhp_output_geometry(&s4, 0, &rb, &gb) == MVHP_SUCCESS);
+                EXPECT(ga.crop_w == gc.crop_w && ga.crop_h == gc.crop_h && ga.out_w == gc.crop_w &&
+                       ga.out_h == std::max(2u, 2 * ((gc.crop_h * 3 + 4) / 8)) && ga.out_h < gc.crop_h);
+                uint32_t fw = 0, fh = 0;
+                EXPECT(mvhp_geometry_fit(ga.out_w, ga.out_h, 40, 40, &fw, &fh) == MVHP_SUCCESS && gb.out_w == fw && gb.out_h == fh);
+            }
+            // every output kind that has RGB x every shape x auto and a forced mode: each picture carries its own setting, batches split
+            // where the setting changes (auto: at every picture of this stream; forced: nowhere, the siting being the same), the
+            // buffers hold n pictures of the geometry, and only what is delivered is downloaded
+            for (int mask : {MVHP_OUT_RGB, MVHP_OUT_RGB_ONLY, MVHP_OUT_PNG})
+                for (uint32_t shape : {0u, (uint32_t)MVHP_OUTPUT_CROP, (uint32_t)(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX), (uint32_t)MVHP_OUTPUT_ASPECT,
+                                       (uint32_t)(MVHP_OUTPUT_ASPECT | MVHP_OUTPUT_BOX), (uint32_t)(MVHP_OUTPUT_ASPECT | MVHP_OUTPUT_ROTATE(1))})
+                    for (int mode : {0, 4}) {
+                        const mvhp_output_request_t req{shape | MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE(mode), 40, 24, 0};
+                        mvhp_output_request_t plain = req;
+                        plain.flags &= ~(MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE_MASK);
+                        mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 64;
+                        CheckC c, c0; mvhp_decode_stats_t st, st0;
+                        const int color0 = g_color_calls;
+                        EXPECT(run_c("color", o, s4, o4, mask, req, c, st) == MVHP_SUCCESS);
+                        EXPECT(c.bad == 0 && c.ok == n4 && g_color_calls - color0 == (int)st.batches && st.d2h_bytes == c.bytes);
+                        const int color1 = g_color_calls;
+                        EXPECT(run_c("the same without the flag", o, s4, o4, mask, plain, c0, st0) == MVHP_SUCCESS);
+                        EXPECT(c0.bad == 0 && c0.ok == n4 && g_color_calls == color1 && st0.d2h_bytes == c0.bytes && st.d2h_bytes == st0.d2h_bytes);
+                        EXPECT(st.geometry_launches == (shape ? st.batches : 0u));
+                        if (mode == 0) {
+                            EXPECT((int)st.batches == n4);   // the setting changes at every picture
+                            if (mask != MVHP_OUT_PNG) { int kinds = 0; for (int k : c.settings_seen) kinds += k > 0; EXPECT(kinds == 2); }
+                        } else {
+                            EXPECT(st.batches == st0.batches);   // one setting: the batches of the request without the flag
+                            if (mask != MVHP_OUT_PNG) { int kinds = 0; for (int k : c.settings_seen) kinds += k > 0; EXPECT(kinds == 1); }
+                        }
+                    }
+            {   // the flag where no RGB is delivered -- planes, JPEG -- changes nothing and runs no colour pass
+                const int color0 = g_color_calls;
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 64;
+                for (uint32_t shape : {0u, (uint32_t)MVHP_OUTPUT_ASPECT}) {
+                    const mvhp_output_request_t req{shape | MVHP_OUTPUT_COLOR, 0, 0, 0}, plain{shape, 0, 0, 0};
+                    CheckC c, c0; mvhp_decode_stats_t st, st0;
+                    EXPECT(run_c("color: planes only", o, s4, o4, 0, req, c, st) == MVHP_SUCCESS && c.bad == 0 && c.ok == n4);
+                    EXPECT(run_c("the same without the flag", o, s4, o4, 0, plain, c0, st0) == MVHP_SUCCESS && c0.bad == 0);
+                    EXPECT(st.batches == st0.batches && st.geometry_launches == st0.geometry_launches && st.d2h_bytes == st0.d2h_bytes);
+                }
+                const mvhp_output_request_t jreq{MVHP_OUTPUT_CROP | MVHP_OUTPUT_COLOR, 0, 0, MVHP_JPEG_REQUEST(80, 0)};
+                mvhp_engine_t *e = nullptr;
+                EXPECT(mvhp_engine_create(&o, &e) == MVHP_SUCCESS);
+                CheckJ cj; mvhp_decode_stats_t st;
+                cj.s = &s4; cj.req = jreq; cj.order = o4;
+                EXPECT(mvhp_engine_decode_ex(e, &s4, o4.data(), n4, n4, MVHP_OUT_JPEG, &jreq, CheckJ::sink, &cj, &st) == MVHP_SUCCESS);
+                mvhp_engine_destroy(e);
+                EXPECT(cj.bad == 0 && cj.ok == (int)st.pictures_ok && cj.ok > 0);
+                EXPECT(g_color_calls == color0);
+            }
+            {   // colour alone at the coded size on a stream without VUI: one setting, the batches of a call without a request
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 3; o.batch_pictures = 7;
+                CheckC c, c0; mvhp_decode_stats_t st, st0;
+                const int geom0 = g_geometry_calls;
+                EXPECT(run_c("color: coded size", o, s, all, MVHP_OUT_RGB, mvhp_output_request_t{MVHP_OUTPUT_COLOR, 0, 0, 0}, c, st) == MVHP_SUCCESS);
+                EXPECT(run_c("the same without the flag", o, s, all, MVHP_OUT_RGB, mvhp_output_request_t{}, c0, st0) == MVHP_SUCCESS);
+                EXPECT(c.bad == 0 && c0.bad == 0 && c.ok == n_idr && st.batches == st0.batches && st.geometry_launches == 0 && g_geometry_calls == geom0);
+            }
+            {   // small batches, three contexts, the first batch of context 0 fails: re-queued with its setting
+                std::vector<int> order;
+                for (int k = 0; k < 3 * n4; k++) order.push_back(k % n4);
+                const mvhp_output_request_t req{MVHP_OUTPUT_ASPECT | MVHP_OUTPUT_BOX | MVHP_OUTPUT_COLOR, 40, 24, 0};
+                mvhp_engine_opts_t o = base; o.contexts = 3; o.chunk_pictures = 2; o.batch_pictures = 3; o.fail_context = 0;
+                CheckC c; mvhp_decode_stats_t st;
+                EXPECT(run_c("color requeue/3ctx", o, s4, order, MVHP_OUT_RGB, req, c, st) == MVHP_SUCCESS);
+                EXPECT(c.bad == 0 && c.ok == (int)order.size() && st.batches_requeued == 1 && st.d2h_bytes == c.bytes);
+            }
+            {   // a device table without the operation: every picture of a call that asks for it fails with the message
+                g_stub.caps &= ~mvengine::CAP_COLOR;
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 4;
+                CheckC c, c0; mvhp_decode_stats_t st;
+                const int color0 = g_color_calls;
+                EXPECT(run_c("color: table without it", o, s4, o4, MVHP_OUT_RGB, mvhp_output_request_t{MVHP_OUTPUT_COLOR, 0, 0, 0}, c, st) == MVHP_FAILURE);
+                EXPECT(c.bad == 0 && c.ok == 0 && c.no_op == n4 && g_color_calls == color0);
+                EXPECT(run_c("color: table without it, planes", o, s4, o4, 0, mvhp_output_request_t{MVHP_OUTPUT_COLOR, 0, 0, 0}, c0, st) == MVHP_SUCCESS && c0.bad == 0 && c0.ok == n4);
+                g_stub.caps |= mvengine::CAP_COLOR;
+            }
+            {   // malformed requests: a colour mode above 4
+                mvhp_engine_opts_t o = base; o.contexts = 1;
+                mvhp_engine_t *e = nullptr;
+                EXPECT(mvhp_engine_create(&o, &e) == MVHP_SUCCESS);
+                const mvhp_output_request_t bad{MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE(5), 0, 0, 0};
+                mvhp_decode_stats_t st;
+                EXPECT(mvhp_engine_decode_ex(e, &s4, o4.data(), n4, n4, MVHP_OUT_RGB, &bad, nullptr, nullptr, &st) == MVHP_FAILURE);
+                mvhp_engine_destroy(e);
+            }
+            {   // minivideo_decode under MINIVIDEO_ASPECT / MINIVIDEO_COLOR: files of the aspect's size, RGB with the picture's setting;
+                // planes are not touched by the colour switch; malformed values fail before the device is touched
+                char tmpl[] = "/tmp/mvharness_XXXXXX";
+                const char *dir = mkdtemp(tmpl);
+                char cwd[4096];
+                EXPECT(dir != nullptr && getcwd(cwd, sizeof(cwd)) != nullptr);
+                std::string in = argv[6];
+                if (in[0] != '/') in = std::string(cwd) + "/" + in;
+                EXPECT(dir && chdir(dir) == 0);
+                struct Sw { const char *aspect, *color; mvhp_output_request_t req; };
+                const Sw sws[] = {{"1", nullptr, mvhp_output_request_t{MVHP_OUTPUT_ASPECT, 0, 0, 0}},
+                                  {"1", "auto", mvhp_output_request_t{MVHP_OUTPUT_ASPECT | MVHP_OUTPUT_COLOR, 0, 0, 0}},
+                                  {nullptr, "bt709-full", mvhp_output_request_t{MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE(4), 0, 0, 0}},
+                                  {"0", "0", mvhp_output_request_t{}}, {"", "", mvhp_output_request_t{}}};
+                for (const Sw &sw : sws)
+                    for (int fmt : {PICTURE_YUV420, PICTURE_BMP}) {
+                        if (sw.aspect) setenv("MINIVIDEO_ASPECT", sw.aspect, 1); else unsetenv("MINIVIDEO_ASPECT");
+                        if (sw.color) setenv("MINIVIDEO_COLOR", sw.color, 1); else unsetenv("MINIVIDEO_COLOR");
+                        MediaFile_t *m = nullptr;
+                        EXPECT(minivideo_open(in.c_str(), &m) == SUCCESS);
+                        EXPECT(m && minivideo_parse(m, false, true, false) == SUCCESS);
+                        const int color0 = g_color_calls;
+                        EXPECT(m && minivideo_decode(m, ".", fmt, 75, n4, PICTURE_UNFILTERED) == SUCCESS);
+                        const bool color = (sw.req.flags & MVHP_OUTPUT_COLOR) != 0 && fmt == PICTURE_BMP;
+                        EXPECT((g_color_calls > color0) == color);
+                        int good = 0;
+                        for (int idr = 0; idr < n4; idr++) {
+                            mvhp_output_geometry_t g;
+                            mvhp_stream_params_t p;
+                            EXPECT(mvhp_output_geometry(&s4, idr, &sw.req, &g) == MVHP_SUCCESS && mvhp_stream_params(&s4, idr, &p) == MVHP_SUCCESS);
+                            const std::string name = std::string(m->file_name) + "_" + std::to_string(idr) + (fmt == PICTURE_BMP ? ".bmp" : ".yuv");
+                            const std::vector<uint8_t> f = read_file(name);
+                            if (f.empty()) continue;
+                            remove(name.c_str());
+                            const uint64_t h = picture_checksum(s4, idr);
+                            const bool coded = g.out_w == p.width_mbs * 16 && g.out_h == p.height_mbs * 16;
+                            uint64_t got = 0;
+                            if (fmt == PICTURE_YUV420) {
+                                if (f.size() != mvhp_geometry_yuv_bytes(&g)) continue;
+                                memcpy(&got, f.data(), 8);
+                                if (got == h && f.back() == (coded ? 0x5a : kLastYuv)) good++;
+                            } else {
+                                const std::vector<uint8_t> rgb = bmp_pixels(f, (int)g.out_w, (int)g.out_h);
+                                if (rgb.size() != mvhp_geometry_rgb_bytes(&g)) continue;
+                                memcpy(&got, rgb.data() + 8, 8);
+                                const uint8_t tag = color ? CheckC::expected_tag(&s4, idr, sw.req, &p, &g) : 0xa5;
+                                if (got == h && rgb[16] == tag && rgb.back() == (color ? kLastColor : coded ? 0xa5 : kLastRgb)) good++;
+                            }
+                        }
+                        printf("%-28s aspect='%s' color='%s' format=%d files right in %d of %d\n", "public API, display", sw.aspect ? sw.aspect : "-",
+                               sw.color ? sw.color : "-", fmt, good, n4);
+                        EXPECT(good == n4);
+                        EXPECT(minivideo_close(&m) == SUCCESS);
+                    }
+                struct Bad { const char *var, *value; };
+                for (const Bad &b : {Bad{"MINIVIDEO_COLOR", "709"}, Bad{"MINIVIDEO_COLOR", "bt709x"}, Bad{"MINIVIDEO_COLOR", "Auto"}, Bad{"MINIVIDEO_COLOR", "1"},
+                                     Bad{"MINIVIDEO_ASPECT", "yes"}, Bad{"MINIVIDEO_ASPECT", "2"}, Bad{"MINIVIDEO_ASPECT", "4:3"}}) {
+                    unsetenv("MINIVIDEO_ASPECT"); unsetenv("MINIVIDEO_COLOR");
+                    setenv(b.var, b.value, 1);
+                    MediaFile_t *m = nullptr;
+                    EXPECT(minivideo_open(in.c_str(), &m) == SUCCESS);
+                    EXPECT(m && minivideo_parse(m, false, true, false) == SUCCESS);
+                    const int ctx_before = g_ctx_created, recon_before = g_recon_calls + g_geometry_calls + g_color_calls;
+                    fflush(stdout);
+                    fflush(stderr);
+                    int pipefd[2];
+                    EXPECT(pipe(pipefd) == 0);
+                    const int saved = dup(2);
+                    dup2(pipefd[1], 2);
+                    const int rc = m ? minivideo_decode(m, ".", PICTURE_BMP, 75, n4, PICTURE_UNFILTERED) : SUCCESS;
+                    fflush(stderr);
+                    dup2(saved, 2);
+                    close(saved);
+                    close(pipefd[1]);
+                    char msg[512] = "";
+                    const ssize_t got = read(pipefd[0], msg, sizeof(msg) - 1);
+                    close(pipefd[0]);
+                    printf("%-28s %s='%s' rc=%d message: %s", "malformed display switch", b.var, b.value, rc, got > 0 ? msg : "(none)\n");
+                    EXPECT(rc == FAILURE && got > 0 && strstr(msg, b.var) != nullptr);
+                    EXPECT(g_ctx_created == ctx_before && g_recon_calls + g_geometry_calls + g_color_calls == recon_before);
+                    EXPECT(minivideo_close(&m) == SUCCESS);
+                }
+                unsetenv("MINIVIDEO_ASPECT"); unsetenv("MINIVIDEO_COLOR");
+                EXPECT(chdir(cwd) == 0);
+                rmdir(dir);
+            }
+            printf("COLOR MODE DONE\n");
         }
         if (argc > 5 && !strcmp(argv[5], "score")) {   // ---- score mode: MVHP_OUTPUT_SCORE against the stub's picture-score operation ----
             std::vector<int> order;

@@ -5,6 +5,8 @@
 //   -c            pictures are the SPS's cropped rectangle (MINIVIDEO_CROP=1)
 //   -s <w>x<h>    ... fitted into a w x h box, never enlarged (MINIVIDEO_THUMBNAIL=<w>x<h>; implies -c)
 //   -r <value>    pictures turned: auto = the MP4's display rotation, or 0 / 90 / 180 / 270 degrees clockwise (MINIVIDEO_ROTATE)
+//   -a            square samples: the VUI's sample aspect ratio is applied (MINIVIDEO_ASPECT=1; implies -c)
+//   -m <value>    RGB by the stream's own colour description (auto) or bt601 / bt709 / bt601-full / bt709-full (MINIVIDEO_COLOR)
 // The stock mini_thumbnailer also builds unchanged against include/minivideo.h; this file exists so
 // that the GPU box (which has no copy of the reference) has a CLI to run.
 #include <minivideo.h>
@@ -63,6 +65,8 @@ int main(int argc, char *argv[])
         } else if (!strcmp(argv[i], "-c")) setenv("MINIVIDEO_CROP", "1", 1);
         else if (!strcmp(argv[i], "-s") && has) setenv("MINIVIDEO_THUMBNAIL", argv[++i], 1);   // (the library checks the value)
         else if (!strcmp(argv[i], "-r") && has) setenv("MINIVIDEO_ROTATE", argv[++i], 1);      // (the library checks the value)
+        else if (!strcmp(argv[i], "-a")) setenv("MINIVIDEO_ASPECT", "1", 1);
+        else if (!strcmp(argv[i], "-m") && has) setenv("MINIVIDEO_COLOR", argv[++i], 1);       // (the library checks the value)
         else if (!strcmp(argv[i], "-j")) setenv("MINIVIDEO_JPEG", "1", 1);   // -f jpg writes JPEG files (made on the GPU), not the PNG fallback
         else if (!strcmp(argv[i], "-z")) setenv("MINIVIDEO_PNG", "1", 1);    // PNG files are compressed, and made on the GPU
         else if (!strcmp(argv[i], "-b")) setenv("MINIVIDEO_SKIP_BLANK", "1", 1);   // blank pictures (black, faded, flat) give way to later ones
@@ -71,7 +75,7 @@ int main(int argc, char *argv[])
     }
     if (!in || help) {
         printf("* Usage:\nmini_thumbnailer -i <filepath> [-o <directory>] [-f picture_format][-q picture_quality]"
-               "[-n picture_number] [-e extraction_mode] [-c] [-s <width>x<height>] [-r auto|0|90|180|270] [-j] [-z] [-b]\n"
+               "[-n picture_number] [-e extraction_mode] [-c] [-s <width>x<height>] [-r auto|0|90|180|270] [-a] [-m auto|bt601|bt709|bt601-full|bt709-full] [-j] [-z] [-b]\n"
                "-z : PNG files (-f png, and -f jpg without -j) are compressed, and made on the GPU (MINIVIDEO_PNG=1)\n"
                "-b : skip blank pictures (MINIVIDEO_SKIP_BLANK=1; MINIVIDEO_BLANK_VARIANCE=<0..16256, default 256>, "
                "MINIVIDEO_BLANK_ALTERNATES=<1..16, default 4>)\n");
