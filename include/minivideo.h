@@ -60,6 +60,23 @@
  *     write fails, the file keeps the picture it had.  The number of files, their names, the return value and picture_number mean
  *     what they mean without the switch, and the files do not depend on batch sizes, threads or devices.  A malformed value
  *     of any of the three variables is not ignored: minivideo_decode() returns FAILURE with a message before any device work;
+ *   - opt-in, outside the reference's behaviour (which writes the coded picture, bars and all) and independent of the switches
+ *     above: MINIVIDEO_TRIM=1 trims the black bars of a letterboxed or pillarboxed stream off every picture (implies
+ *     MINIVIDEO_CROP).  Bars are a property of the stream, not of a picture -- a dark scene has no edge, and pictures of
+ *     differing sizes are of no use -- so up to MINIVIDEO_TRIM_PROBES (1 ... 64, default 8) of the selected pictures, spread evenly
+ *     over the selection and the first among them, are decoded first and measured on the GPU: a luma sample is bright above
+ *     MINIVIDEO_TRIM_LEVEL (1 ... 254, default 24: video black plus noise), a row or column of the SPS's cropped rectangle is
+ *     content when at least 1/32 of its samples (at least one) are bright, and a picture's box spans its first to its last
+ *     content row and column (a subtitle burnt into a bar keeps its rows).  The union of the probes' boxes, its edges moved
+ *     outward to even, replaces the cropped rectangle of EVERY picture -- unless less than half of the width or of the height
+ *     would be left (a dark scene, not a bar) or no probe shows content: then, and for a picture of another size in
+ *     mid-stream, the files are exactly those of MINIVIDEO_CROP=1.  Everything else starts from the trimmed rectangle: a
+ *     MINIVIDEO_THUMBNAIL box is fitted to it, MINIVIDEO_ASPECT and MINIVIDEO_ROTATE apply to it, the score of
+ *     MINIVIDEO_SKIP_BLANK is taken over it.  The number of files, their names, the return value and picture_number mean what
+ *     they mean without the switch, Annex-B and MP4 input behave alike, and the files do not depend on batch sizes, threads or
+ *     devices.  Cost: the probes are entropy-decoded twice, at most MINIVIDEO_TRIM_PROBES pictures per call.  0 and the empty
+ *     string for MINIVIDEO_TRIM are the files without the switch; a malformed value of any of the three variables is not
+ *     ignored: minivideo_decode() returns FAILURE with a message before any device work;
  *   - H.264 IDR pictures only, from Annex-B elementary streams (.264/.h264 or a
  *     file starting with an SPS start code) or from the first H.264 video track
  *     of an MP4/MOV file (demuxer/mp4/mp4.c:1950 mp4_fileParse -> sync samples).

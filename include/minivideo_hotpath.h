@@ -332,6 +332,20 @@ typedef struct mvhp_output_geometry {
 #define MVHP_OUTPUT_COLOR_MODE_SHIFT 8
 #define MVHP_OUTPUT_COLOR_MODE_MASK  0x700u
 #define MVHP_OUTPUT_COLOR_MODE(m) (((uint32_t)(m) & 7u) << MVHP_OUTPUT_COLOR_MODE_SHIFT)
+/* Black bars (opt-in; "Black bars" below).  MVHP_OUTPUT_TRIM (implies MVHP_OUTPUT_CROP): crop_* of a picture's geometry is
+ * mvhp_trim_rect(the picture's SPS crop, the box the stream carries -- mvhp_stream_set_trim); aspect, box and the turn's exchange of
+ * sides follow unchanged and start from that rectangle.  A picture for which the rule says 0 (another SPS in mid-stream, a
+ * different size) keeps its SPS crop: trimming never fails a picture.  With no box set the flag is MVHP_OUTPUT_CROP.
+ * MVHP_OUTPUT_BARS (mvhp_engine_decode_ex only) probes: behind whatever reconstructs the batch (and the deblocking filter)
+ * mvhp_luma_bars_dev runs over each picture's crop rectangle on the coded planes, the 32-byte records come back with the pictures
+ * and the sink finds g->reserved[0] = x | y << 16 and g->reserved[1] = w | h << 16 (sides are at most 16384).  Those words are the
+ * file length and the score elsewhere: the flag is refused together with MVHP_OUT_JPEG, MVHP_OUT_PNG, MVHP_OUTPUT_SCORE and the
+ * plain sink of mvhp_engine_decode.  The level travels in bits 24-31 of mvhp_output_request_t::reserved (MVHP_BARS_REQUEST; 0 = 24).
+ * The flag changes no picture: a request with this flag alone still means pictures of the coded size; d2h_bytes grows by exactly
+ * 32 per delivered picture. */
+#define MVHP_OUTPUT_BARS 0x1000u
+#define MVHP_OUTPUT_TRIM 0x2000u
+#define MVHP_BARS_REQUEST(level) (((uint32_t)(level) & 0xffu) << 24)
 typedef struct mvhp_output_request {
     uint32_t flags;           /* MVHP_OUTPUT_*; 0 = the coded size (what the reference writes)                  */
     uint32_t box_w, box_h;
@@ -546,6 +560,52 @@ MVHP_EXPORT int      mvhp_blank_choose(const uint32_t *scores, int n, uint32_t m
 MVHP_EXPORT int      mvhp_luma_stats_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
                                          const uint8_t *d_yuv_coded, int n, mvhp_luma_stats_t *d_stats, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Black bars (opt-in; DESIGN.md 3 "Black bars"): where the content of a letterboxed or pillarboxed picture lies, found on the
+ * device by counting, so that a caller can trim the bars (minivideo_decode does under MINIVIDEO_TRIM=1, include/minivideo.h).
+ * A sample is bright when Y > level (1 ... 254; 24 = video black 16 plus noise).  Row y of a rectangle cw x ch is content when at
+ * least mvhp_bars_need(cw) of its samples are bright, column x when at least mvhp_bars_need(ch) of its samples are.  Integers
+ * only: a record is a function of the samples alone.  Bars are a property of the stream, not of a picture (a dark scene has no
+ * edge): a caller probes a few pictures, unites their boxes (mvhp_bars_union), lets mvhp_trim_rect decide whether to trust the
+ * union and hands it to the stream (mvhp_stream_set_trim), where MVHP_OUTPUT_TRIM applies it to every picture alike.
+ * ------------------------------------------------------------------------- */
+typedef struct mvhp_luma_bars {   /* 32 bytes, 8-byte aligned */
+    uint32_t x, y, w, h;          /* box of the content rows / columns, luma samples, CODED-picture coordinates: x the first content
+                                     column, x + w - 1 the last, likewise rows (the box spans first to last: bars in the middle of
+                                     a picture are not bars); w = h = 0 (and x = y = 0): no content row or no content column */
+    uint32_t rows, cols;          /* how many rows / columns of the rectangle are content (they need not be contiguous); reported
+                                     also for an empty box */
+    uint32_t reserved[2];         /* 0 */
+} mvhp_luma_bars_t;
+#define MVHP_BARS_LEVEL_DEFAULT 24
+/* max(1, len >> 5): bright samples that make a row of `len` samples (a column of `len` rows) content.  A host function. */
+MVHP_EXPORT uint32_t mvhp_bars_need(uint32_t len);
+/* The smallest box that holds every non-empty box of b[0..n) into *out (rows = cols = 0; empty when there is none); returns the
+ * number of non-empty boxes.  Commutative: the order of b does not matter.  A host function. */
+MVHP_EXPORT int      mvhp_bars_union(const mvhp_luma_bars_t *b, int n, mvhp_luma_bars_t *out);
+/* The trim rule.  `u` is intersected with the rectangle crop_* of `crop` (even, as every crop is); the left and top edge move
+ * down to even, the right and bottom edge up to even (the result stays inside the crop); the trimmed rectangle is accepted only
+ * when its width is at least (cw + 1) / 2 and its height at least (ch + 1) / 2 -- a detection that would throw away more than
+ * half of a side is a dark scene, not a bar.  Accepted: out->crop_* is the trimmed rectangle, returns 1.  Otherwise (also for an
+ * empty u or an empty intersection): out->crop_* is the crop, returns 0.  Either way out_w / out_h = crop_w / crop_h and
+ * reserved = 0; out may be crop.  A host function. */
+MVHP_EXPORT int      mvhp_trim_rect(const mvhp_output_geometry_t *crop, const mvhp_luma_bars_t *u, mvhp_output_geometry_t *out);
+/* The stream carries one box in coded coordinates, read only by mvhp_output_geometry under MVHP_OUTPUT_TRIM: setting it changes
+ * nothing by itself.  u == NULL or an empty box clears it.  mvhp_stream_trim copies it out (empty when none is set).  Not
+ * thread-safe against a decode call that runs on the stream: set it between calls. */
+MVHP_EXPORT int      mvhp_stream_set_trim(mvhp_stream_t *s, const mvhp_luma_bars_t *u);
+MVHP_EXPORT int      mvhp_stream_trim(const mvhp_stream_t *s, mvhp_luma_bars_t *out);
+/* n coded pictures (d_yuv_coded: mvhp_yuv_frame_bytes(p) apart, 16-byte aligned, luma pitch 16 W) -> n records in d_bars (8-byte
+ * aligned), each over the luma rectangle crop_x, crop_y, crop_w, crop_h of g (all even, inside the coded picture, at least
+ * 2 x 2; out_w / out_h are not read).  n = 0 does nothing; a level outside 1 ... 254, n < 0, a rectangle outside the picture, odd
+ * or zero sizes and NULL or misaligned pointers are refused (MVHP_FAILURE) before anything is launched.  Asynchronous on `stream`
+ * (NULL = the context's own).  The row and column counters live in a scratch buffer of the context (4 (cw + ch) bytes per
+ * picture), which the call zeroes on that stream itself: two calls of one context run one after the other, whatever their
+ * streams.  No kernel waits and nothing survives the call but the records: safe under stream capture once the scratch buffer
+ * has its size. */
+MVHP_EXPORT int      mvhp_luma_bars_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                                        const uint8_t *d_yuv_coded, int n, int level, mvhp_luma_bars_t *d_bars, void *stream);
+
 /* Page-locked host memory for the host-buffer entry points (H2D / D2H at full PCIe rate). */
 MVHP_EXPORT void *mvhp_host_alloc(size_t bytes);
 MVHP_EXPORT void  mvhp_host_free(void *p);
@@ -593,6 +653,12 @@ MVHP_EXPORT int  mvhp_set_crop_copy(mvhp_ctx_t *ctx, int on);
  * mvhp_luma_stats_dev, 1 ... 65536; 0 (default) = sixteen, fewer when the grid would leave compute units idle.  It exists so that
  * a test can force band sizes and compare the records: the sums are integers, every value gives the same 32 bytes. */
 MVHP_EXPORT int  mvhp_set_stats_band(mvhp_ctx_t *ctx, int rows);
+
+/* Test-only knob, like the one above (speed only, never results; not meant for products): luma rows per workgroup of the counting
+ * pass of mvhp_luma_bars_dev, 1 ... 65536; 0 (default) = choose from the batch (few, tall bands where there are many pictures,
+ * short ones where the grid would leave compute units idle).  It exists so that a test can force band sizes and compare the
+ * records: the counts are integers, every value gives the same 32 bytes. */
+MVHP_EXPORT int  mvhp_set_bars_band(mvhp_ctx_t *ctx, int rows);
 
 /* Tuning knob (speed only, never results): waves per picture workgroup, or macroblock rows per band of the banded forms
  * (1, 2, 4, 6, 8, 12 or 16; a layout that is not built for the value takes the next smaller one it is built for, or its

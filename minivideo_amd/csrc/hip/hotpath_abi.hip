@@ -61,6 +61,7 @@ struct mvhp_ctx {
     int          fused_color; // 1 = RGB written by the reconstruction kernel's epilogue (default)
     int          crop_copy;   // 1 = crop-only geometries run the copy kernel (crop_copy.hip), 0 = the general resample kernel
     int          stats_band;  // luma rows per workgroup of the picture-score kernel, 0 = choose (mvhp_set_stats_band)
+    int          bars_band;   // luma rows per workgroup of the black-bar counting pass, 0 = choose (mvhp_set_bars_band)
     int          n_cus;
     size_t       max_lds;
     int          last_layout, last_waves;   // what the last reconstruction launch used
@@ -92,6 +93,11 @@ struct mvhp_ctx {
     size_t       d_png_bytes;
     hipEvent_t   png_done;
     hipStream_t  png_stream;
+    // black bars (luma_bars.hip): row and column counters of one batch, kept like the encoders' scratch
+    void        *d_bars;
+    size_t       d_bars_bytes;
+    hipEvent_t   bars_done;
+    hipStream_t  bars_stream;
 };
 
 static hipStream_t stream_of(const mvhp_ctx *c, void *stream) { return stream ? (hipStream_t)stream : c->stream; }
@@ -176,6 +182,8 @@ MVHP_EXPORT void mvhp_destroy(mvhp_ctx_t *c)
     if (c->jpeg_done) hipEventDestroy(c->jpeg_done);
     if (c->d_png) hipFree(c->d_png);
     if (c->png_done) hipEventDestroy(c->png_done);
+    if (c->d_bars) hipFree(c->d_bars);
+    if (c->bars_done) hipEventDestroy(c->bars_done);
     if (c->wide_done) hipEventDestroy(c->wide_done);
     hipStreamDestroy(c->stream);
     delete c;
@@ -228,6 +236,13 @@ MVHP_EXPORT int mvhp_set_stats_band(mvhp_ctx_t *c, int rows)
 {
     if (!c || rows < 0 || rows > 65536) return MVHP_FAILURE;
     c->stats_band = rows;
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT int mvhp_set_bars_band(mvhp_ctx_t *c, int rows)
+{
+    if (!c || rows < 0 || rows > 65536) return MVHP_FAILURE;
+    c->bars_band = rows;
     return MVHP_SUCCESS;
 }
 
@@ -612,6 +627,57 @@ MVHP_EXPORT int mvhp_luma_stats_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p
     return MVHP_SUCCESS;
 }
 
+MVHP_EXPORT int mvhp_luma_bars_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                                   const uint8_t *d_yuv_coded, int n, int level, mvhp_luma_bars_t *d_bars, void *stream)
+{
+    if (!c || !params_ok(p) || !g || !d_yuv_coded || n < 0 || ((uintptr_t)d_yuv_coded & 15) || !d_bars || ((uintptr_t)d_bars & 7)) {
+        set_err("mvhp_luma_bars_dev: invalid argument");
+        return MVHP_FAILURE;
+    }
+    if (level < 1 || level > 254) {
+        set_err("mvhp_luma_bars_dev: level %d (1 ... 254)", level);
+        return MVHP_FAILURE;
+    }
+    const uint32_t Wp = p->width_mbs * 16, Hp = p->height_mbs * 16;
+    if (((g->crop_x | g->crop_y | g->crop_w | g->crop_h) & 1u) || g->crop_w < 2 || g->crop_h < 2 || g->crop_x > Wp ||
+        g->crop_w > Wp - g->crop_x || g->crop_y > Hp || g->crop_h > Hp - g->crop_y) {
+        set_err("mvhp_luma_bars_dev: rectangle %u,%u %ux%u of a %ux%u picture (even offsets and sizes of at least 2, inside the picture)",
+                g->crop_x, g->crop_y, g->crop_w, g->crop_h, Wp, Hp);
+        return MVHP_FAILURE;
+    }
+    if (n == 0) return MVHP_SUCCESS;
+    HIP_TRY(hipSetDevice(c->device));
+    mvhp::LumaBarsArgs a{};
+    a.src = d_yuv_coded;
+    a.frame_bytes = mvhp_yuv_frame_bytes(p);
+    a.n = n;
+    a.pitch = (int)Wp;
+    a.cx = (int)g->crop_x; a.cy = (int)g->crop_y; a.cw = (int)g->crop_w; a.ch = (int)g->crop_h;
+    a.level = level;
+    // luma rows per workgroup of the counting pass.  Every band adds its column counts to the picture's counters, cw atomic adds
+    // a band, so: as few bands as the kernel's LDS tile of 1024 rows gives (1080p: two of 540 rows -- 2048 pictures issue 8 M
+    // adds, not the 260 M of sixteen-row bands), doubled while the grid would leave compute units idle and a band keeps sixteen
+    // rows.  Speed only: the counts are integers, any band size gives the same record.
+    int band = c->bars_band;
+    if (band <= 0) {
+        int bands = (a.ch + 1023) / 1024;
+        while ((double)n * bands < 4.0 * c->n_cus && (a.ch + 2 * bands - 1) / (2 * bands) >= 16) bands *= 2;
+        band = (a.ch + bands - 1) / bands;
+    }
+    a.band = band;
+    a.bars = d_bars;
+    const hipStream_t st = stream_of(c, stream);
+    const size_t need = mvhp::luma_bars_scratch_bytes(a);
+    if (!c->bars_done) HIP_TRY(hipEventCreateWithFlags(&c->bars_done, hipEventDisableTiming));
+    if (ensure(&c->d_bars, &c->d_bars_bytes, need) != MVHP_SUCCESS) return MVHP_FAILURE;   // (hipFree waits for the device)
+    if (c->bars_stream && c->bars_stream != st) HIP_TRY(hipStreamWaitEvent(st, c->bars_done, 0));
+    a.scratch = (uint32_t *)c->d_bars;
+    HIP_TRY(mvhp::launch_luma_bars(a, st));
+    HIP_TRY(hipEventRecord(c->bars_done, st));
+    c->bars_stream = st;
+    return MVHP_SUCCESS;
+}
+
 MVHP_EXPORT size_t mvhp_jpeg_header_bytes(void) { return MVHP_JPEG_HEADER_BYTES; }
 
 MVHP_EXPORT int mvhp_jpeg_quant_tables(int quality, uint8_t out[128])
@@ -982,6 +1048,12 @@ int eng_run_batch(DevCtx *d, const mvengine::BatchJob &j, mvengine::BatchDone &d
         whole.crop_h = whole.out_h = p->height_mbs * 16;
         rc = mvhp_luma_stats_dev(c, p, j.geom ? j.geom : &whole, j.d_yuv, j.n, j.stats, c->stream);
     }
+    if (rc == MVHP_SUCCESS && j.bars) {
+        mvhp_output_geometry_t whole{};
+        whole.crop_w = whole.out_w = p->width_mbs * 16;
+        whole.crop_h = whole.out_h = p->height_mbs * 16;
+        rc = mvhp_luma_bars_dev(c, p, j.geom ? j.geom : &whole, j.d_yuv, j.n, j.bars_level, j.bars, c->stream);
+    }
     if (rc != MVHP_SUCCESS) { err = mvhp_last_error(); return rc; }
     ENG_TRY(hipEventRecord(d->ev[3], c->stream));
     std::string ew;
@@ -1034,7 +1106,7 @@ void eng_placed_free(DevCtx *d, void *arena)
 
 const mvengine::DeviceApi g_hip_api = {
     mvhp_device_count, mvhp_host_alloc, mvhp_host_free, eng_ctx_create, eng_ctx_destroy, eng_dev_alloc, eng_dev_free,
-    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_COLOR | mvengine::CAP_PNG,
+    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_COLOR | mvengine::CAP_PNG | mvengine::CAP_BARS,
     eng_placed_alloc, eng_placed_free,
 };
 

@@ -180,4 +180,20 @@ struct LumaStatsArgs {
 };
 hipError_t launch_luma_stats(const LumaStatsArgs &a, hipStream_t stream);
 
+// black bars (luma_bars.hip): the box of the content rows and columns of one rectangle of every picture
+struct LumaBarsArgs {
+    const uint8_t     *src;          // n coded pictures, 16-byte aligned
+    size_t             frame_bytes;  // from one picture to the next (a multiple of 16)
+    int                n;
+    int                pitch;        // of the luma plane, a multiple of 16
+    int                cx, cy, cw, ch;   // the rectangle, inside the picture, cw and ch at least 1
+    int                band;         // luma rows per workgroup of the counting pass
+    int                level;        // 1 .. 254: a sample is bright when it is above
+    uint32_t          *scratch;      // luma_bars_scratch_bytes(), 4-byte aligned
+    uint32_t          *cols, *rows;  // (set by the launch function: the two parts of scratch)
+    mvhp_luma_bars_t  *bars;         // n records, 8-byte aligned
+};
+size_t     luma_bars_scratch_bytes(const LumaBarsArgs &a);
+hipError_t launch_luma_bars(const LumaBarsArgs &a, hipStream_t stream);
+
 } // namespace mvhp

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "decode_engine.h"
+#include "bars_policy.h"
 #include "blank_policy.h"
 #include "export.h"
 #include "h264_frontend.h"
@@ -623,6 +624,14 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
         if (!mvblank::settings_from(getenv("MINIVIDEO_SKIP_BLANK"), getenv("MINIVIDEO_BLANK_VARIANCE"),
                                     getenv("MINIVIDEO_BLANK_ALTERNATES"), blank, why)) { log_err("%s", why.c_str()); return FAILURE; }
     }
+    mvbars::Settings trim;
+    {   // and for the black-bar switches
+        std::string why;
+        if (!mvbars::settings_from(getenv("MINIVIDEO_TRIM"), getenv("MINIVIDEO_TRIM_LEVEL"), getenv("MINIVIDEO_TRIM_PROBES"), trim, why)) {
+            log_err("%s", why.c_str());
+            return FAILURE;
+        }
+    }
 
     // The engine (HIP runtime, one context per device, its thread pools: 0.2-0.5 s in a fresh process) comes up on a thread
     // of its own while this one reads and indexes the file.
@@ -721,6 +730,49 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     std::vector<ExportSink::Slot> slots;
     if (blank.on) { req.flags |= MVHP_OUTPUT_SCORE; sink.slots = &slots; }
     const int out_kind = jpeg ? MVHP_OUT_JPEG : png_dev ? MVHP_OUT_PNG : want_rgb ? MVHP_OUT_RGB_ONLY : 0;
+    if (trim.on) {
+        // opt-in (MINIVIDEO_TRIM=1, outside the parity contract): black bars are a property of the stream, so a few pictures of
+        // the list are probed first -- order[floor(k size / P)], k = 0 .. P - 1, the first picture among them -- in one call that
+        // only collects their content boxes; the union of the boxes travels with the stream and MVHP_OUTPUT_TRIM applies it to
+        // every picture of the calls below alike.  The probes are entropy-decoded twice: at most MINIVIDEO_TRIM_PROBES pictures
+        // per call.  The union is commutative and the probes are a function of the list: the files do not depend on batch
+        // sizes, threads or contexts.  A probe that fails to decode is simply missing.
+        struct ProbeSink {
+            std::vector<mvhp_luma_bars_t> boxes;
+            static int call(void *user, int, int, int rc, const char *, const mvhp_stream_params_t *, const mvhp_output_geometry_t *g,
+                            const uint8_t *, const uint8_t *)
+            {
+                if (rc != MVHP_SUCCESS || !g) return 0;
+                mvhp_luma_bars_t b{};
+                b.x = g->reserved[0] & 0xffffu; b.y = g->reserved[0] >> 16;
+                b.w = g->reserved[1] & 0xffffu; b.h = g->reserved[1] >> 16;
+                ((ProbeSink *)user)->boxes.push_back(b);
+                return 1;
+            }
+        } probe;
+        const double t_probe = wall_s();
+        const size_t size = order.size(), P = std::min<size_t>((size_t)trim.probes, size);
+        std::vector<int> probes;
+        for (size_t k = 0; k < P; k++) probes.push_back(order[k * size / P]);
+        mvhp_output_request_t preq{};
+        preq.flags = MVHP_OUTPUT_CROP | MVHP_OUTPUT_BARS;
+        preq.reserved = MVHP_BARS_REQUEST(trim.level);
+        mvhp_decode_stats_t pst;
+        memset(&pst, 0, sizeof(pst));
+        (void)mvhp_engine_decode_ex(eng, &s, probes.data(), (int)P, (int)P, 0, &preq, ProbeSink::call, &probe, &pst);
+        mvhp_luma_bars_t u{};
+        const int with_content = mvhp_bars_union(probe.boxes.data(), (int)probe.boxes.size(), &u);
+        (void)mvhp_stream_set_trim(&s, with_content ? &u : nullptr);
+        req.flags |= MVHP_OUTPUT_TRIM;
+        if (getenv("MINIVIDEO_STATS")) {
+            mvhp_output_geometry_t crop{}, cut{};
+            const int applied = mvhp_stream_crop(&s, order[0], &crop) == MVHP_SUCCESS && mvhp_trim_rect(&crop, &u, &cut);
+            fprintf(stderr, "[minivideo] black bars: %d probes listed, %d decoded, %d with content above %d; union %u,%u %ux%u, %s "
+                            "(first picture: %u,%u %ux%u), %.3f s\n", (int)P, (int)probe.boxes.size(), with_content, trim.level,
+                    u.x, u.y, u.w, u.h, applied ? "applied" : "not applied", cut.crop_x, cut.crop_y, cut.crop_w, cut.crop_h,
+                    wall_s() - t_probe);
+        }
+    }
     (void)mvhp_engine_decode_ex(eng, &s, order.data(), (int)order.size(), wanted, out_kind,
                                 (req.flags || jpeg) ? &req : nullptr, ExportSink::call, &sink, &st);   // (MVHP_OUT_PNG has no parameters)
     sink.finish();   // (every kept picture is back: mvhp_engine_decode waits for that)

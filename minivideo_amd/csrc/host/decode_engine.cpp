@@ -150,7 +150,7 @@ enum BufKind {
     kMidYuv,     // a batch that scales AND turns: the resampled planes before the turn (the turn reads them, nothing downloads them)
     kJpegBlob,   // MVHP_OUT_JPEG: the encoder's blob (n x the raw picture); MVHP_OUT_PNG: n x the longest file ...
     kJpegTab,    // ... and table of a batch
-    kStats,      // MVHP_OUTPUT_SCORE: the records of a batch (n x 32 bytes)
+    kStats,      // MVHP_OUTPUT_SCORE or MVHP_OUTPUT_BARS (never both): the records of a batch (n x 32 bytes)
     kBufKinds,
     kArenaKinds = kOutYuv,
 };
@@ -190,6 +190,8 @@ struct Wants {
     int turns = 0;                  // quarter turns the request applies (mvhp_output_turns): one value per call
     bool color = false;             // MVHP_OUTPUT_COLOR in a call that delivers RGB or PNG: the RGB comes from a colour pass over the
                                     // final planes (which a batch with a geometry then keeps, whether or not they are downloaded)
+    bool bars = false;              // MVHP_OUTPUT_BARS (it changes no picture and no path; never beside score, jpeg or png)
+    int bars_level = MVHP_BARS_LEVEL_DEFAULT;
 };
 // whether a batch of the DELIVERED geometry g, turned by `turns`, has a resample pass in front of the turn
 bool scales_before_turn(const mvhp_output_geometry_t &g, int turns)
@@ -222,7 +224,7 @@ size_t picture_bytes(BufKind k, const mvhp_stream_params_t &p, const mvhp_output
     case kMidYuv:   return use_geom && scales_before_turn(g, w.turns) ? mvhp_geometry_yuv_bytes(&g) : 0;
     case kJpegBlob: return w.jpeg ? mvhp_geometry_yuv_bytes(&g) : w.png ? png_blob_bytes(g) : 0;
     case kJpegTab:  return w.jpeg || w.png ? sizeof(mvhp_jpeg_entry_t) : 0;
-    case kStats:    return w.score ? sizeof(mvhp_luma_stats_t) : 0;
+    case kStats:    return w.score ? sizeof(mvhp_luma_stats_t) : w.bars ? sizeof(mvhp_luma_bars_t) : 0;
     default:        return 0;
     }
 }
@@ -999,6 +1001,7 @@ void Engine::launcher(int k)
         const double t_call = now_s();
         if (inject) err = "injected failure (test hook)";
         else if (w_.score && !(api_.caps & CAP_SCORE)) err = "this device table has no picture-score operation";
+        else if (w_.bars && !(api_.caps & CAP_BARS)) err = "this device table has no black-bar operation";
         else if (w_.jpeg && !(api_.caps & CAP_JPEG)) err = "this device table has no JPEG operation";
         else if (w_.png && !(api_.caps & CAP_PNG)) err = "this device table has no PNG operation";
         else if (b->use_geom && !w_.jpeg && !(api_.caps & CAP_GEOMETRY)) err = "this device table has no output-geometry operation";
@@ -1025,7 +1028,9 @@ void Engine::launcher(int k)
             job.blob = buf(kJpegBlob);
             job.blob_cap = (size_t)b->total * need(*b, kJpegBlob);
             job.table = (mvhp_jpeg_entry_t *)buf(kJpegTab);
-            job.stats = (mvhp_luma_stats_t *)buf(kStats);
+            job.stats = w_.score ? (mvhp_luma_stats_t *)buf(kStats) : nullptr;
+            job.bars = w_.bars ? (mvhp_luma_bars_t *)buf(kStats) : nullptr;
+            job.bars_level = w_.bars_level;
             rc = api_.run_batch(cx.dev, job, done, err);
         }
         const float ms = done.ms;
@@ -1121,7 +1126,9 @@ void Engine::downloader(int k)
                 fail = "out of page-locked host memory";
                 continue;
             }
-            if (sb) recs = (const mvhp_luma_stats_t *)oc->stats.p;
+            const mvhp_luma_bars_t *boxes = nullptr;   // MVHP_OUTPUT_BARS: the same piece, the other record
+            if (sb && w_.score) recs = (const mvhp_luma_stats_t *)oc->stats.p;
+            if (sb && w_.bars) boxes = (const mvhp_luma_bars_t *)oc->stats.p;
             if (w_.jpeg || w_.png) {   // the table rows of the chunk's pictures, then exactly the bytes they name, one piece per file
                 const mvhp_jpeg_entry_t *tab = nullptr;
                 const size_t tb = need(*b, kJpegTab);
@@ -1219,6 +1226,10 @@ void Engine::downloader(int k)
                         r.yuv = yb ? oc->yuv.p + (size_t)i * yb : nullptr;
                         r.rgb = rb ? oc->rgb.p + (size_t)i * rb : nullptr;
                         if (recs) r.geom.reserved[1] = mvblank::luma_score(recs[i].sum, recs[i].sumsq, recs[i].samples);
+                        if (boxes) {   // (sides are at most 16384: two to a word)
+                            r.geom.reserved[0] = boxes[i].x | boxes[i].y << 16;
+                            r.geom.reserved[1] = boxes[i].w | boxes[i].h << 16;
+                        }
                         r.ready = true;
                         oc->refs++;
                     }
@@ -1250,7 +1261,7 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
                    mvhp_picture_sink_t sink, mvhp_picture_sink_ex_t sink_ex, void *user, mvhp_decode_stats_t *stats,
                    std::string &err)
 {
-    if (req && ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_SCORE | MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK | MVHP_OUTPUT_ASPECT | MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE_MASK)) ||
+    if (req && ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_SCORE | MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK | MVHP_OUTPUT_ASPECT | MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE_MASK | MVHP_OUTPUT_BARS | MVHP_OUTPUT_TRIM)) ||
                 ((req->flags & MVHP_OUTPUT_COLOR_MODE_MASK) >> MVHP_OUTPUT_COLOR_MODE_SHIFT) > 4 || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2)))) {
         err = "malformed output request (box sides must be at least 2, colour modes are 0 to 4)";
         return MVHP_FAILURE;
@@ -1263,6 +1274,15 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         err = sink ? "MVHP_OUT_PNG needs mvhp_engine_decode_ex: its sink gets the file's length with the geometry"
                    : "MVHP_OUT_PNG and MVHP_OUT_JPEG are two output kinds: a call delivers one";
         return MVHP_FAILURE;
+    }
+    if (req && (req->flags & MVHP_OUTPUT_BARS)) {   // the box travels in the two words that are the file length and the score elsewhere
+        const char *why = sink ?"MVHP_OUTPUT_BARS needs mvhp_engine_decode_ex: its sink gets the box with the geometry"
+                          : (out_mask & MVHP_OUT_JPEG) ? "MVHP_OUTPUT_BARS and MVHP_OUT_JPEG both use g->reserved[0]: a call delivers one"
+                          : (out_mask & MVHP_OUT_PNG) ? "MVHP_OUTPUT_BARS and MVHP_OUT_PNG both use g->reserved[0]: a call delivers one"
+                          : (req->flags & MVHP_OUTPUT_SCORE) ? "MVHP_OUTPUT_BARS and MVHP_OUTPUT_SCORE both use g->reserved[1]: a call delivers one" : nullptr;
+        if (why) { err = why; return MVHP_FAILURE; }
+        const uint32_t level = req->reserved >> 24;
+        if (level == 255) { err = "MVHP_OUTPUT_BARS: level 255 (1 ... 254; 0 = 24)"; return MVHP_FAILURE; }
     }
     if (!order || n_order <= 0 || wanted <= 0) { err = "nothing to decode"; return MVHP_FAILURE; }
     for (int i = 0; i < n_order; i++)
@@ -1284,7 +1304,9 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         }
         req_ = req ? *req : mvhp_output_request_t{};
         w_.score = (req_.flags & MVHP_OUTPUT_SCORE) != 0;
-        req_.flags &= ~MVHP_OUTPUT_SCORE;   // (what is left decides the geometry: none = the path of a call without a request)
+        w_.bars = (req_.flags & MVHP_OUTPUT_BARS) != 0;
+        w_.bars_level = (req_.reserved >> 24) ? (int)(req_.reserved >> 24) : MVHP_BARS_LEVEL_DEFAULT;
+        req_.flags &= ~(MVHP_OUTPUT_SCORE | MVHP_OUTPUT_BARS);   // (what is left decides the geometry: none = the path of a call without a request)
         // colour: only where the call delivers RGB or PNG; otherwise, and always for the geometry, the request without the bits
         w_.color = (req_.flags & MVHP_OUTPUT_COLOR) != 0 && (w_.rgb || w_.png);
         color_mode_ = (int)((req_.flags & MVHP_OUTPUT_COLOR_MODE_MASK) >> MVHP_OUTPUT_COLOR_MODE_SHIFT);

@@ -50,6 +50,8 @@ struct BatchJob {
                                         // size -- and `png` reads that RGB.  Never beside `jpeg`
     mvhp_luma_stats_t *stats;   // NULL: no picture scores.  Else mvhp_luma_stats_dev over the crop rectangle of `geom` (the whole
                                 // picture without one) on the n coded planes in d_yuv -> n records
+    mvhp_luma_bars_t *bars;     // NULL: no black-bar probe.  Else mvhp_luma_bars_dev at `bars_level` over the same rectangle of the
+    int bars_level;             // same planes -> n records (never beside `stats`, `jpeg` or `png`)
 };
 struct BatchDone {
     float ms;            // device-side duration of the whole job, one bracketed interval
@@ -57,7 +59,7 @@ struct BatchDone {
 };
 
 // what run_batch can do beyond pictures of the coded size; a job that needs a missing bit fails in the engine, with a message
-enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4, CAP_ORIENT = 8, CAP_PNG = 16, CAP_COLOR = 32 };
+enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4, CAP_ORIENT = 8, CAP_PNG = 16, CAP_COLOR = 32, CAP_BARS = 64 };
 
 // Every operation blocks its calling thread until the device has finished it; the engine runs one thread per queue
 // and context, which is what overlaps upload(k+1), kernel(k) and download(k-1).  *ms = device-side duration.

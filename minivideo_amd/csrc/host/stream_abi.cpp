@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../hip/resample_taps.h"
+#include "bars_policy.h"
 #include "h264_frontend.h"
 #include "mp4_demux.h"
 #include "stream_internal.h"
@@ -402,11 +403,16 @@ MVHP_EXPORT int mvhp_output_geometry(const mvhp_stream_t *s, int idr, const mvhp
         out->crop_h = out->out_h = p.height_mbs * 16;
         return MVHP_SUCCESS;
     }
-    if ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_ASPECT)) || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2))) {
+    if ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_ASPECT | MVHP_OUTPUT_TRIM)) || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2))) {
         g_stream_err = "mvhp_output_geometry: malformed request (box sides must be at least 2)";
         return MVHP_FAILURE;
     }
     if (mvhp_stream_crop(s, idr, out) != MVHP_SUCCESS) return MVHP_FAILURE;
+    if ((req->flags & MVHP_OUTPUT_TRIM) && s->trim[2] && s->trim[3]) {   // black bars: the stream's box, where the rule trusts it
+        mvhp_luma_bars_t u{};
+        u.x = s->trim[0]; u.y = s->trim[1]; u.w = s->trim[2]; u.h = s->trim[3];
+        mvbars::trim_rect(*out, &u, *out);   // (0: this picture keeps its SPS crop)
+    }
     if (req->flags & MVHP_OUTPUT_ASPECT) {   // square samples first: one axis of the crop shrinks; the box is fitted to that size
         const Sps &sps = s->idrs[idr].sps;
         mvrs::aspect(out->crop_w, out->crop_h, sps.sar_w, sps.sar_h, out->out_w, out->out_h);
@@ -415,6 +421,42 @@ MVHP_EXPORT int mvhp_output_geometry(const mvhp_stream_t *s, int idr, const mvhp
         const uint32_t dw = out->out_w, dh = out->out_h;
         mvrs::fit(dw, dh, req->box_w, req->box_h, out->out_w, out->out_h);
     }
+    return MVHP_SUCCESS;
+}
+
+// ---- black bars (host only; include/minivideo_hotpath.h "Black bars") ----
+
+MVHP_EXPORT uint32_t mvhp_bars_need(uint32_t len) { return mvbars::need(len); }
+
+MVHP_EXPORT int mvhp_bars_union(const mvhp_luma_bars_t *b, int n, mvhp_luma_bars_t *out)
+{
+    mvhp_luma_bars_t u;
+    const int found = mvbars::unite(b, n, u);
+    if (out) *out = u;
+    return found;
+}
+
+MVHP_EXPORT int mvhp_trim_rect(const mvhp_output_geometry_t *crop, const mvhp_luma_bars_t *u, mvhp_output_geometry_t *out)
+{
+    if (!crop || !out) return 0;
+    const mvhp_output_geometry_t c = *crop;
+    return mvbars::trim_rect(c, u, *out);
+}
+
+MVHP_EXPORT int mvhp_stream_set_trim(mvhp_stream_t *s, const mvhp_luma_bars_t *u)
+{
+    if (!s) return MVHP_FAILURE;
+    const bool none = !u || mvbars::empty(*u);
+    s->trim[0] = none ? 0 : u->x; s->trim[1] = none ? 0 : u->y;
+    s->trim[2] = none ? 0 : u->w; s->trim[3] = none ? 0 : u->h;
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT int mvhp_stream_trim(const mvhp_stream_t *s, mvhp_luma_bars_t *out)
+{
+    if (!s || !out) return MVHP_FAILURE;
+    memset(out, 0, sizeof(*out));
+    out->x = s->trim[0]; out->y = s->trim[1]; out->w = s->trim[2]; out->h = s->trim[3];
     return MVHP_SUCCESS;
 }
 

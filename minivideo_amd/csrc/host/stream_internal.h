@@ -23,6 +23,7 @@ struct mvhp_stream {
     bool spec = false;            // MVHP_STREAM_SPEC: standard-conformant index + luma-DC rule (opt-in, outside parity)
     int quarter_turns = 0;        // MP4: clockwise quarter turns of the video track's tkhd matrix (0 for Annex B)
     bool deblock = false;         // MVHP_STREAM_DEBLOCK: records carry the deblocking fields, params ask for the filter
+    uint32_t trim[4] = {0, 0, 0, 0};   // mvhp_stream_set_trim: x, y, w, h of the content box, coded coordinates; w = h = 0: none
 
     int build(std::string &err);      // Annex-B elementary stream
     int build_mp4(std::string &err);  // ISO-BMFF: avcC parameter sets + length-prefixed NAL units of the sync samples

@@ -62,6 +62,8 @@ OUTPUT_ASPECT, OUTPUT_COLOR, OUTPUT_COLOR_MODE_SHIFT = 0x800, 0x80, 8     # ... 
 MATRIX_BT601, MATRIX_BT709 = 0, 1                                       # mvhp_color_params_t::matrix (MVHP_MATRIX_*)
 CHROMA_NEAREST, CHROMA_LEFT, CHROMA_CENTER = 0, 1, 2                    # mvhp_color_params_t::siting (MVHP_CHROMA_*)
 COLOR_MODES = ("auto", "bt601", "bt709", "bt601-full", "bt709-full")    # MVHP_OUTPUT_COLOR_MODE(index); MINIVIDEO_COLOR's values
+OUTPUT_BARS, OUTPUT_TRIM, BARS_LEVEL_SHIFT = 0x1000, 0x2000, 24           # ... probe the black bars (level in reserved bits 24-31); trim them
+BARS_LEVEL_DEFAULT = 24                                                 # MVHP_BARS_LEVEL_DEFAULT
 ORIENT_SRC_CODED = 1                                                    # mvhp_orient_dev src_flags (MVHP_ORIENT_SRC_CODED)
 
 
@@ -97,6 +99,12 @@ class OutputGeometry(C.Structure):
         """the picture's score (Engine.decode(score=True): MVHP_OUTPUT_SCORE), else 0"""
         return int(self.reserved[1])
 
+    @property
+    def bars(self):
+        """the picture's content box (x, y, w, h) in coded coordinates (Engine.decode(bars=...): MVHP_OUTPUT_BARS); w = h = 0: none"""
+        a, b = int(self.reserved[0]), int(self.reserved[1])
+        return a & 0xffff, a >> 16, b & 0xffff, b >> 16
+
 
 class OutputRequest(C.Structure):
     """mvhp_output_request_t"""
@@ -112,14 +120,14 @@ def color_flags(color):
     return OUTPUT_COLOR | (COLOR_MODES.index(color) << OUTPUT_COLOR_MODE_SHIFT)
 
 
-def output_request(output, rotate=None, aspect=False, color=None):
+def output_request(output, rotate=None, aspect=False, color=None, trim=False):
     """None -> None (the coded size); "crop" -> the SPS crop; (w, h) -> the crop fitted into a w x h box.  rotate (see
     rotate_flags()) adds the orientation bits; with rotate given the result is never None.  aspect=True adds
     MVHP_OUTPUT_ASPECT (square samples; implies the crop), color (see color_flags()) the colour bits; with either the result is
-    never None"""
-    rot = rotate_flags(rotate) | (OUTPUT_ASPECT if aspect else 0) | color_flags(color)
+    never None.  trim=True adds MVHP_OUTPUT_TRIM (the stream's content box, stream_set_trim(); implies the crop)"""
+    rot = rotate_flags(rotate) | (OUTPUT_ASPECT if aspect else 0) | color_flags(color) | (OUTPUT_TRIM if trim else 0)
     if output is None:
-        return OutputRequest(rot, 0, 0, 0) if (rotate is not None or aspect or color is not None) else None
+        return OutputRequest(rot, 0, 0, 0) if (rotate is not None or aspect or color is not None or trim) else None
     if output == "crop":
         return OutputRequest(OUTPUT_CROP | rot, 0, 0, 0)
     w, h = output
@@ -199,6 +207,66 @@ def blank_choose(scores, min_score):
     """mvhp_blank_choose: index of the first score >= min_score, else of the largest (the earliest on a tie); -1 for none"""
     arr = (C.c_uint32 * max(len(scores), 1))(*[int(x) for x in scores])
     return int(lib().mvhp_blank_choose(arr, len(scores), int(min_score)))
+
+
+class LumaBars(C.Structure):
+    """mvhp_luma_bars_t: the box of the content rows and columns of a picture's rectangle, coded coordinates"""
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("rows", C.c_uint32),
+                ("cols", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    def as_tuple(self):
+        return int(self.x), int(self.y), int(self.w), int(self.h), int(self.rows), int(self.cols)
+
+
+LUMA_BARS_DTYPE = np.dtype([("x", "<u4"), ("y", "<u4"), ("w", "<u4"), ("h", "<u4"), ("rows", "<u4"), ("cols", "<u4"),
+                            ("reserved", "<u4", (2,))])
+
+
+def _as_bars(b):
+    if b is None or isinstance(b, LumaBars):
+        return b
+    t = tuple(int(v) for v in b)
+    return LumaBars(*t[:4]) if len(t) == 4 else LumaBars(*t[:6])
+
+
+def bars_need(length):
+    """mvhp_bars_need: bright samples that make a row of `length` samples (a column of `length` rows) content (no device needed)"""
+    return int(lib().mvhp_bars_need(int(length)))
+
+
+def bars_union(boxes):
+    """mvhp_bars_union over LumaBars records or (x, y, w, h) tuples: (number of non-empty boxes, LumaBars of their union)"""
+    recs = [_as_bars(b) for b in boxes]
+    arr = (LumaBars * max(len(recs), 1))(*recs)
+    out = LumaBars()
+    n = int(lib().mvhp_bars_union(arr, len(recs), C.byref(out)))
+    return n, out
+
+
+def trim_rect(crop, union):
+    """mvhp_trim_rect: (accepted 0 / 1, OutputGeometry) for the OutputGeometry `crop` and the LumaBars or (x, y, w, h) `union`"""
+    out = OutputGeometry()
+    u = _as_bars(union)
+    rc = int(lib().mvhp_trim_rect(C.byref(crop), C.byref(u) if u is not None else None, C.byref(out)))
+    return rc, out
+
+
+def stream_set_trim(stream_handle, union):
+    """mvhp_stream_set_trim: the stream carries the box (a LumaBars or (x, y, w, h)); None or an empty box clears it"""
+    u = _as_bars(union)
+    if lib().mvhp_stream_set_trim(stream_handle, C.byref(u) if u is not None else None) != SUCCESS:
+        raise MiniVideoError("mvhp_stream_set_trim failed")
+
+
+def stream_trim(stream_handle):
+    """mvhp_stream_trim: the box the stream carries as (x, y, w, h); w = h = 0: none"""
+    out = LumaBars()
+    if lib().mvhp_stream_trim(stream_handle, C.byref(out)) != SUCCESS:
+        raise MiniVideoError("mvhp_stream_trim failed")
+    return out.as_tuple()[:4]
+
+
+set_trim, trim = stream_set_trim, stream_trim   # (the stream-level pair under the library's verbs)
 
 
 def geometry(crop_x, crop_y, crop_w, crop_h, out_w=None, out_h=None):
@@ -284,10 +352,10 @@ def geometry_aspect(cw, ch, sar_w, sar_h):
     return ow.value, oh.value
 
 
-def output_geometry(stream_handle, idr, output, rotate=None, aspect=False):
-    """mvhp_output_geometry under output_request(output, rotate, aspect), or None: what the sink gets"""
+def output_geometry(stream_handle, idr, output, rotate=None, aspect=False, trim=False):
+    """mvhp_output_geometry under output_request(output, rotate, aspect, trim=trim), or None: what the sink gets"""
     g = OutputGeometry()
-    req = output_request(output, rotate, aspect)
+    req = output_request(output, rotate, aspect, trim=trim)
     rc = lib().mvhp_output_geometry(stream_handle, int(idr), C.byref(req) if req is not None else None, C.byref(g))
     return g if rc == SUCCESS else None
 
@@ -397,6 +465,21 @@ def lib():
     L.mvhp_luma_stats_dev.argtypes = [vp, pp, pg, vp, i32, vp, vp]
     L.mvhp_set_stats_band.restype = i32
     L.mvhp_set_stats_band.argtypes = [vp, i32]
+    pb = C.POINTER(LumaBars)
+    L.mvhp_bars_need.restype = u32
+    L.mvhp_bars_need.argtypes = [u32]
+    L.mvhp_bars_union.restype = i32
+    L.mvhp_bars_union.argtypes = [pb, i32, pb]
+    L.mvhp_trim_rect.restype = i32
+    L.mvhp_trim_rect.argtypes = [pg, pb, pg]
+    L.mvhp_stream_set_trim.restype = i32
+    L.mvhp_stream_set_trim.argtypes = [vp, pb]
+    L.mvhp_stream_trim.restype = i32
+    L.mvhp_stream_trim.argtypes = [vp, pb]
+    L.mvhp_luma_bars_dev.restype = i32
+    L.mvhp_luma_bars_dev.argtypes = [vp, pp, pg, vp, i32, i32, vp, vp]
+    L.mvhp_set_bars_band.restype = i32
+    L.mvhp_set_bars_band.argtypes = [vp, i32]
     L.mvhp_jpeg_header_bytes.restype = sz
     L.mvhp_jpeg_header_bytes.argtypes = []
     L.mvhp_jpeg_quant_tables.restype = i32
@@ -538,6 +621,18 @@ class HotPath:
         rc = self._L.mvhp_luma_stats_dev(self._h, C.byref(params), C.byref(geom), d_yuv_coded, int(n), d_stats, stream)
         if rc != SUCCESS:
             raise _err(self._L, "mvhp_luma_stats_dev")
+
+    def luma_bars_dev(self, params, geom, d_yuv_coded, n, level, d_bars, stream=None):
+        """n coded pictures (device) -> n LumaBars records (LUMA_BARS_DTYPE, device) over geom's crop rectangle: a sample is bright
+        when it is above `level` (1 .. 254).  Asynchronous."""
+        rc = self._L.mvhp_luma_bars_dev(self._h, C.byref(params), C.byref(geom), d_yuv_coded, int(n), int(level), d_bars, stream)
+        if rc != SUCCESS:
+            raise _err(self._L, "mvhp_luma_bars_dev")
+
+    def set_bars_band(self, rows):
+        """test-only: luma rows per workgroup of luma_bars_dev's counting pass, 0 = choose (speed only: the records do not depend on it)"""
+        if self._L.mvhp_set_bars_band(self._h, int(rows)) != SUCCESS:
+            raise MiniVideoError("mvhp_set_bars_band(%d) failed" % rows)
 
     def set_stats_band(self, rows):
         """test-only: luma rows per workgroup of luma_stats_dev, 0 = choose (speed only: the records do not depend on it)"""
@@ -712,7 +807,7 @@ class Engine:
         self._L.mvhp_engine_release_picture(self._h, int(seq))
 
     def decode(self, stream_handle, order, wanted=None, want_rgb=False, sink=None, output=None, jpeg=None, restart_mcus=0,
-               score=False, rotate=None, png=False, aspect=False, color=None):
+               score=False, rotate=None, png=False, aspect=False, color=None, bars=None, trim=False):
         """sink(seq, idr, rc, err, params, yuv ndarray | None, rgb ndarray | None) -> 1 accept / 0 reject / -1 stop /
         2 accept and keep until release_picture(seq); the arrays are views of page-locked memory valid only during the call
         (or until the release).  Returns (rc, stats dict).
@@ -730,16 +825,33 @@ class Engine:
         turned on the device; the sink is called as for `output`, and its geometry is the one of the turned picture.
         aspect=True: MVHP_OUTPUT_ASPECT -- the stream's sample aspect ratio is applied (square samples out); implies the crop.
         color = "auto" or "bt601" / "bt709" / "bt601-full" / "bt709-full": MVHP_OUTPUT_COLOR -- the RGB (and the PNG files) are
-        made from the final planes by the stream's own matrix, range and chroma siting, or by the forced matrix and range."""
+        made from the final planes by the stream's own matrix, range and chroma siting, or by the forced matrix and range.
+        bars = True (level 24) or a level 1 .. 254: MVHP_OUTPUT_BARS -- the sink is called as for `output` and finds each picture's
+        content box in geometry.bars; the pictures are the same bytes.  Not together with jpeg, png or score, and it needs a
+        sink (ValueError).
+        trim=True: MVHP_OUTPUT_TRIM -- the crop of every picture is trimmed to the box the stream carries (stream_set_trim())
+        where the trim rule accepts it; implies the crop."""
         order = (C.c_int * len(order))(*order)
         st = DecodeStats()
         n_wanted = len(order) if wanted is None else wanted
         if png and jpeg is not None:
             raise ValueError("png and jpeg are two output kinds: a call delivers one")
-        if output is not None or jpeg is not None or score or rotate is not None or png or aspect or color is not None:
-            req = output_request(output, rotate, aspect, color) or OutputRequest(0, 0, 0, 0)
+        probe = bars is not None and bars is not False
+        if probe:
+            level = BARS_LEVEL_DEFAULT if bars is True else int(bars)
+            if not 1 <= level <= 254:
+                raise ValueError("bars must be True or a level between 1 and 254")
+            if jpeg is not None or png or score:
+                raise ValueError("bars travels in the geometry words that carry the file length and the score: not together with jpeg, png or score")
+            if sink is None:
+                raise ValueError("bars needs a sink: the boxes are delivered with the geometry")
+        if output is not None or jpeg is not None or score or rotate is not None or png or aspect or color is not None or probe or trim:
+            req = output_request(output, rotate, aspect, color, trim=bool(trim)) or OutputRequest(0, 0, 0, 0)
             if score:
                 req.flags |= OUTPUT_SCORE
+            if probe:
+                req.flags |= OUTPUT_BARS
+                req.reserved = level << BARS_LEVEL_SHIFT
             if jpeg is not None:
                 req.reserved = (min(max(int(jpeg), 1), 100) & 0xff) | ((int(restart_mcus) & 0xffff) << 8)
 

@@ -127,6 +127,23 @@ mvhp_luma_stats_t expected_stats(uint64_t h, bool pattern, const mvhp_stream_par
     return st;
 }
 
+// The box the stub's black-bar operation reports for a picture (bars mode): inside the rectangle, a function of the records'
+// checksum, so that every picture has its own; every seventh checksum gives the empty box.
+mvhp_luma_bars_t expected_bars(uint64_t h, const mvhp_output_geometry_t *g)
+{
+    mvhp_luma_bars_t b{};
+    const uint32_t cw = g->crop_w, ch = g->crop_h;
+    if (h % 7 == 0 || cw < 2 || ch < 2) return b;
+    const uint32_t ox = (uint32_t)(h % (cw / 2)), oy = (uint32_t)((h >> 8) % (ch / 2));
+    b.x = g->crop_x + ox;
+    b.y = g->crop_y + oy;
+    b.w = cw - ox - (uint32_t)((h >> 16) % ((cw - ox + 1) / 2));
+    b.h = ch - oy - (uint32_t)((h >> 24) % ((ch - oy + 1) / 2));
+    b.rows = b.h;
+    b.cols = b.w;
+    return b;
+}
+
 // The one batch operation.  Every job expands its pictures and leaves coded planes; then, as the descriptor asks:
 // * nothing more (pictures of the coded size): the planes are the output, 0x5a with the checksum of the records in bytes 0-7; RGB
 //   0xa5 with the checksum in bytes 8-15;
@@ -143,12 +160,17 @@ mvhp_luma_stats_t expected_stats(uint64_t h, bool pattern, const mvhp_stream_par
 //   be there to read, else d_rgb of the coded size -- is stamped as above, with the setting in byte 16 (0xc0 | matrix << 3 |
 //   full_range << 2 | siting) and 0x7b last; planes of the coded size stay the output they are without the pass;
 // * scores: honest sums over the rectangle of the coded planes the batch buffer holds.
+// * black bars (bars mode): never beside scores, JPEG or PNG; the level must be 1 .. 254 and is remembered; every picture gets
+//   expected_bars() of its records over the rectangle of the geometry (the coded picture without one).
 // * PNG: the RGB the encoder reads is stamped as above (the fused RGB of a batch of the coded size, the resample or turn target
 //   otherwise; no output planes), and every picture gets a "file" of 64 + checksum % (the longest file - 64) bytes of 0x3d that
 //   starts with bytes 8-15 of that RGB (the checksum) and ends in 0x7a; the blob must be n x the longest file rounded to 16, so
 //   no picture is too big.
 constexpr uint8_t kLastYuv = 0x77, kLastRgb = 0x78, kLastJpeg = 0x79, kLastPng = 0x7a, kLastColor = 0x7b;
 std::atomic<int> g_jpeg_calls{0}, g_stats_calls{0}, g_orient_calls{0}, g_mid_calls{0}, g_png_calls{0}, g_color_calls{0};
+std::atomic<int> g_bars_calls{0}, g_bars_level{0};
+std::atomic<uint32_t> g_watch_crop[4];   // bars mode: launches whose geometry has this crop rectangle are counted
+std::atomic<int> g_watch_hits{0};
 uint8_t color_tag(const mvhp_color_params_t &c) { return (uint8_t)(0xc0 | (c.matrix << 3) | (c.full_range << 2) | c.siting); }
 size_t stub_png_room(const mvhp_output_geometry_t *g) { return (mvhp::png_max_bytes((int)g->out_w, (int)g->out_h) + 15) & ~(size_t)15; }
 size_t stub_png_length(uint64_t h, const mvhp_output_geometry_t *g) { return 64 + (size_t)(h % (mvhp::png_max_bytes((int)g->out_w, (int)g->out_h) - 64)); }
@@ -200,6 +222,12 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
     if (g) rect = *g;
     if (j.stats && (n <= 0 || rect.crop_w == 0 || rect.crop_h == 0 || rect.crop_x + rect.crop_w > p->width_mbs * 16 ||
                     rect.crop_y + rect.crop_h > p->height_mbs * 16)) { err = "stub: picture-score launch without buffers or rectangle"; return MVHP_FAILURE; }
+    if (j.bars && (j.stats || j.jpeg || j.png || j.bars_level < 1 || j.bars_level > 254 || n <= 0 || rect.crop_w == 0 || rect.crop_h == 0 ||
+                   rect.crop_x + rect.crop_w > p->width_mbs * 16 || rect.crop_y + rect.crop_h > p->height_mbs * 16)) {
+        err = "stub: black-bar launch without buffers, level or rectangle";
+        return MVHP_FAILURE;
+    }
+    if (g && g->crop_x == g_watch_crop[0] && g->crop_y == g_watch_crop[1] && g->crop_w == g_watch_crop[2] && g->crop_h == g_watch_crop[3]) g_watch_hits++;
     for (int i = 0; i < n; i++)
         expand_compact((const uint8_t *)j.d_compact + (size_t)i * j.stride, (size_t)p->width_mbs * p->height_mbs, (uint8_t *)j.d_packed + (size_t)i * pb);
     if (j.jpeg && j.out_yuv) memset(j.out_yuv, 0x12, (size_t)n * gy);
@@ -265,18 +293,20 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
             st.samples = rect.crop_w * rect.crop_h;
             j.stats[i] = st;
         }
+        if (j.bars) j.bars[i] = expected_bars(h, &rect);
     }
     std::this_thread::sleep_for(std::chrono::microseconds(200));
     done.ms = j.stats ? 0.25f : 0.2f;
     done.layout = MVHP_LAYOUT_ROWS;
     done.waves = 8;
     if (j.stats) g_stats_calls++;
+    if (j.bars) { g_bars_calls++; g_bars_level = j.bars_level; }
     return MVHP_SUCCESS;
 }
 
 mvengine::DeviceApi g_stub = {stub_device_count, stub_host_alloc, stub_host_free, stub_ctx_create, stub_ctx_destroy,
                                     stub_dev_alloc, stub_dev_free, stub_dev_free_bytes, stub_copy_n, stub_copy_n, stub_run_batch,
-                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_PNG | mvengine::CAP_COLOR,
+                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_PNG | mvengine::CAP_COLOR | mvengine::CAP_BARS,
                                     nullptr, nullptr};   // (no placed arena on the stub device)
 
 uint64_t picture_checksum(const mvhp_stream &s, int idr)
@@ -579,6 +609,52 @@ struct CheckS {
         return 1;
     }
 };
+
+// sink of the bars mode: what CheckG checks of the picture, and the picture's own box in the two reserved words
+struct CheckB {
+    const mvhp_stream *s = nullptr;
+    mvhp_output_request_t req{};   // without MVHP_OUTPUT_BARS: what decides the geometry
+    int mask = 0;
+    int calls = 0, ok = 0, failed = 0, bad = 0, next_seq = 0, formed_n = 0, no_op = 0, empty = 0;
+    std::vector<int> order;
+    std::vector<uint64_t> boxes;
+    static int sink(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                    const uint8_t *yuv, const uint8_t *rgb)
+    {
+        CheckB &c = *static_cast<CheckB *>(user);
+        c.calls++;
+        if (seq != c.next_seq || idr != c.order[(size_t)seq] || !g) c.bad++;
+        c.next_seq = seq + 1;
+        mvhp_output_geometry_t want;
+        const bool formed = mvhp_output_geometry(c.s, idr, &c.req, &want) == MVHP_SUCCESS;
+        if (formed) c.formed_n++;
+        const uint64_t h = picture_checksum(*c.s, idr);
+        if (rc != MVHP_SUCCESS) {
+            c.failed++;
+            if (err && strstr(err, "black-bar operation")) c.no_op++;
+            else if (!err || !*err || yuv || rgb || formed) c.bad++;
+            return 0;
+        }
+        if (!formed) { c.bad++; return 0; }
+        const bool coded = want.crop_x == 0 && want.crop_y == 0 && want.out_w == p->width_mbs * 16 && want.out_h == p->height_mbs * 16 &&
+                           want.crop_w == want.out_w && want.crop_h == want.out_h;
+        const mvhp_luma_bars_t b = expected_bars(h, &want);
+        want.reserved[0] = b.x | b.y << 16;
+        want.reserved[1] = b.w | b.h << 16;
+        if (memcmp(&want, g, sizeof(want)) != 0) { c.bad++; return 0; }
+        if (b.w == 0) c.empty++;
+        c.boxes.push_back((uint64_t)g->reserved[0] << 32 | g->reserved[1]);
+        uint64_t got = 0;
+        const bool want_rgb = (c.mask & 1) != 0, want_yuv = !want_rgb || (c.mask & 2) == 0;
+        if ((yuv != nullptr) != want_yuv || (rgb != nullptr) != want_rgb) { c.bad++; return 0; }
+        if (yuv) { memcpy(&got, yuv, 8); if (got != h || yuv[mvhp_geometry_yuv_bytes(g) - 1] != (coded ? 0x5a : kLastYuv)) c.bad++; }
+        if (rgb) { memcpy(&got, rgb + 8, 8); if (got != h || rgb[mvhp_geometry_rgb_bytes(g) - 1] != (coded ? 0xa5 : kLastRgb)) c.bad++; }
+        c.ok++;
+        return 1;
+    }
+};
+
+int plain_sink_accepts(void *, int, int, int rc, const char *, const mvhp_stream_params_t *, const uint8_t *, const uint8_t *) { return rc == MVHP_SUCCESS; }
 
 std::vector<uint8_t> read_file(const std::string &path)
 {
@@ -1796,6 +1872,213 @@ int main(int argc, char **argv)
             }
             unsetenv("MINIVIDEO_SKIP_BLANK");
             printf("SCORE MODE DONE\n");
+        }
+        if (argc > 5 && !strcmp(argv[5], "bars")) {   // ---- bars mode: MVHP_OUTPUT_BARS / MVHP_OUTPUT_TRIM against the stub's black-bar operation ----
+            std::vector<int> order;
+            for (int k = 0; k < 3 * n3; k++) order.push_back(k % n3);
+            auto run_bars = [&](const char *name, mvhp_engine_opts_t o, int mask, mvhp_output_request_t req, CheckB &c, mvhp_decode_stats_t &stats) {
+                mvhp_engine_t *e = nullptr;
+                if (mvhp_engine_create(&o, &e) != MVHP_SUCCESS) { failures++; return MVHP_FAILURE; }
+                c.s = &s3; c.req = req; c.req.reserved = 0; c.order = order; c.mask = mask;
+                req.flags |= MVHP_OUTPUT_BARS;
+                const int rc = mvhp_engine_decode_ex(e, &s3, order.data(), (int)order.size(), (int)order.size(), mask, &req, CheckB::sink, &c, &stats);
+                mvhp_engine_destroy(e);
+                printf("%-28s rc=%d mask=%d flags=%u ok=%u failed=%u batches=%u geometry=%u requeued=%u d2h=%llu\n", name, rc, mask, req.flags,
+                       stats.pictures_ok, stats.pictures_failed, stats.batches, stats.geometry_launches, stats.batches_requeued,
+                       (unsigned long long)stats.d2h_bytes);
+                return rc;
+            };
+            int distinct_checked = 0, empty_seen = 0;
+            for (int contexts = 1; contexts <= 3; contexts++)
+                for (int mask : {0, MVHP_OUT_RGB, MVHP_OUT_RGB_ONLY})
+                    for (mvhp_output_request_t req : {mvhp_output_request_t{0, 0, 0, 0}, crop, box}) {
+                        mvhp_engine_opts_t o = base; o.contexts = contexts; o.chunk_pictures = 2; o.batch_pictures = contexts == 1 ? 64 : 3;
+                        // without the flag: the two words are 0 (CheckG compares all of the geometry) and the operation is never called
+                        mvhp_decode_stats_t st0;
+                        const int calls0 = g_bars_calls;
+                        CheckG cg;
+                        EXPECT(run_ex("bars: flag off", o, s3, order, mask, req, cg, st0) == MVHP_SUCCESS);
+                        EXPECT(cg.bad == 0 && g_bars_calls == calls0);
+                        // with it (three contexts: the first batch of context 0 fails and is re-queued, and probed again)
+                        o.fail_context = contexts == 3 ? 0 : -1;
+                        const int level = contexts == 2 ? 37 : 0;   // (0 means 24)
+                        req.reserved = MVHP_BARS_REQUEST(level);
+                        const int launches0 = g_recon_calls + g_geometry_calls;
+                        CheckB c; mvhp_decode_stats_t st;
+                        EXPECT(run_bars(req.flags & MVHP_OUTPUT_BOX ? "bars box" : req.flags ? "bars crop" : "bars coded size", o, mask, req, c, st) == MVHP_SUCCESS);
+                        EXPECT(c.bad == 0 && c.no_op == 0 && c.calls == (int)order.size() && c.ok == (int)st.pictures_ok && c.ok + c.failed == c.calls);
+                        EXPECT(c.ok == (int)st0.pictures_ok);
+                        EXPECT(st.d2h_bytes == st0.d2h_bytes + 32ull * (uint64_t)c.formed_n);   // exactly one record per picture of a batch
+                        EXPECT((int)st.batches_requeued == (contexts == 3 ? 1 : 0));
+                        EXPECT(g_bars_calls - calls0 == (int)st.batches);                          // every launch of such a call carries `bars`
+                        EXPECT(g_recon_calls + g_geometry_calls - launches0 == (int)st.batches);
+                        EXPECT(g_bars_level == (level ? level : MVHP_BARS_LEVEL_DEFAULT));
+                        if (!req.flags) EXPECT(st.geometry_launches == 0);   // the flag alone: still the coded-size path
+                        std::vector<uint64_t> d = c.boxes;
+                        std::sort(d.begin(), d.end());
+                        if (std::unique(d.begin(), d.end()) - d.begin() >= 3) distinct_checked++;
+                        empty_seen += c.empty;
+                    }
+            EXPECT(distinct_checked == 27);   // the sink got each picture's own box
+            printf("%-28s %d empty boxes delivered\n", "bars", empty_seen);
+            {   // a device table without the operation: every picture of the call fails with the message
+                g_stub.caps &= ~mvengine::CAP_BARS;
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 4;
+                CheckB c; mvhp_decode_stats_t st;
+                const int calls0 = g_bars_calls, recon0 = g_recon_calls + g_geometry_calls;
+                EXPECT(run_bars("bars: table without it", o, 0, crop, c, st) == MVHP_FAILURE);
+                EXPECT(c.bad == 0 && c.ok == 0 && c.no_op == c.formed_n && c.no_op > 0 && g_bars_calls == calls0);
+                EXPECT(g_recon_calls + g_geometry_calls == recon0);
+                CheckG cg;   // ... and a call without the flag is not affected
+                EXPECT(run_ex("bars: table without it, off", o, s3, order, 0, crop, cg, st) == MVHP_SUCCESS && cg.bad == 0);
+                g_stub.caps |= mvengine::CAP_BARS;
+            }
+            {   // the four refusals, each with a message and before any work
+                mvhp_engine_opts_t o = base; o.contexts = 1;
+                std::string why;
+                mvengine::Engine *pe = mvengine::engine_create(g_stub, &o, why);
+                EXPECT(pe != nullptr);
+                const int launches0 = g_recon_calls + g_geometry_calls + g_jpeg_calls + g_png_calls + g_bars_calls;
+                struct Refused { const char *name; int mask; uint32_t flags; const char *word; };
+                for (const Refused &r : {Refused{"bars with JPEG", MVHP_OUT_JPEG, MVHP_OUTPUT_BARS, "MVHP_OUT_JPEG"},
+                                         Refused{"bars with PNG", MVHP_OUT_PNG, MVHP_OUTPUT_BARS | MVHP_OUTPUT_CROP, "MVHP_OUT_PNG"},
+                                         Refused{"bars with the score", 0, MVHP_OUTPUT_BARS | MVHP_OUTPUT_SCORE, "MVHP_OUTPUT_SCORE"}}) {
+                    mvhp_output_request_t req{r.flags, 0, 0, 0};
+                    CheckB c; c.s = &s3; c.order = order; mvhp_decode_stats_t st;
+                    why.clear();
+                    const int rc = pe ? mvengine::engine_decode(pe, s3, order.data(), (int)order.size(), (int)order.size(), r.mask, &req, nullptr,
+                                                                CheckB::sink, &c, &st, why) : MVHP_SUCCESS;
+                    printf("%-28s rc=%d message: %s\n", r.name, rc, why.c_str());
+                    EXPECT(rc == MVHP_FAILURE && c.calls == 0 && why.find(r.word) != std::string::npos && why.find("MVHP_OUTPUT_BARS") != std::string::npos);
+                }
+                {   // a level of 255
+                    mvhp_output_request_t req{MVHP_OUTPUT_BARS, 0, 0, MVHP_BARS_REQUEST(255)};
+                    CheckB c; c.s = &s3; c.order = order; mvhp_decode_stats_t st;
+                    why.clear();
+                    EXPECT(pe && mvengine::engine_decode(pe, s3, order.data(), (int)order.size(), (int)order.size(), 0, &req, nullptr, CheckB::sink, &c, &st,
+                                                         why) == MVHP_FAILURE && c.calls == 0 && why.find("255") != std::string::npos);
+                }
+                {   // the plain sink has no geometry to carry the box
+                    mvhp_output_request_t req{MVHP_OUTPUT_BARS, 0, 0, 0};
+                    mvhp_decode_stats_t st;
+                    why.clear();
+                    const int rc = pe ? mvengine::engine_decode(pe, s3, order.data(), (int)order.size(), (int)order.size(), 0, &req, plain_sink_accepts,
+                                                                nullptr, nullptr, &st, why) : MVHP_SUCCESS;
+                    printf("%-28s rc=%d message: %s\n", "bars with the plain sink", rc, why.c_str());
+                    EXPECT(rc == MVHP_FAILURE && why.find("MVHP_OUTPUT_BARS") != std::string::npos && why.find("mvhp_engine_decode_ex") != std::string::npos);
+                }
+                if (pe) mvengine::engine_destroy(pe);
+                EXPECT(g_recon_calls + g_geometry_calls + g_jpeg_calls + g_png_calls + g_bars_calls == launches0);
+            }
+            {   // MVHP_OUTPUT_TRIM with a box set on the stream: the geometry is launched with the trimmed rectangle; without the
+                // flag, or without a box, with the SPS crop
+                mvhp_luma_bars_t u{};
+                u.x = 3; u.y = 9; u.w = 70; u.h = 55;
+                mvhp_output_geometry_t sps{}, cut{};
+                EXPECT(mvhp_stream_crop(&s3, 0, &sps) == MVHP_SUCCESS && mvhp_trim_rect(&sps, &u, &cut) == 1);
+                EXPECT(memcmp(&sps, &cut, sizeof(sps)) != 0);
+                g_watch_crop[0] = cut.crop_x; g_watch_crop[1] = cut.crop_y; g_watch_crop[2] = cut.crop_w; g_watch_crop[3] = cut.crop_h;
+                const mvhp_output_request_t trim{MVHP_OUTPUT_TRIM, 0, 0, 0}, trim_box{MVHP_OUTPUT_TRIM | MVHP_OUTPUT_BOX, 40, 40, 0};
+                for (int contexts = 1; contexts <= 3; contexts++) {
+                    mvhp_engine_opts_t o = base; o.contexts = contexts; o.chunk_pictures = 2; o.batch_pictures = contexts == 1 ? 64 : 3;
+                    o.fail_context = contexts == 3 ? 0 : -1;
+                    mvhp_decode_stats_t st, st_crop;
+                    g_watch_hits = 0;
+                    CheckG c0;   // no box set: the flag is MVHP_OUTPUT_CROP (CheckG forms the geometry it expects from the same stream)
+                    EXPECT(run_ex("trim: no box", o, s3, order, 0, trim, c0, st) == MVHP_SUCCESS && c0.bad == 0 && g_watch_hits == 0);
+                    CheckG cc;
+                    EXPECT(run_ex("trim: crop for comparison", o, s3, order, 0, crop, cc, st_crop) == MVHP_SUCCESS && cc.bad == 0);
+                    EXPECT(st.d2h_bytes == st_crop.d2h_bytes && st.geometry_launches == st_crop.geometry_launches);
+                    EXPECT(mvhp_stream_set_trim(&s3, &u) == MVHP_SUCCESS);
+                    CheckG c1;   // a box set, no flag: nothing changes
+                    EXPECT(run_ex("trim: box, flag off", o, s3, order, 0, crop, c1, st) == MVHP_SUCCESS && c1.bad == 0 && g_watch_hits == 0);
+                    EXPECT(st.d2h_bytes == st_crop.d2h_bytes);
+                    for (const mvhp_output_request_t &req : {trim, trim_box}) {
+                        for (int mask : {0, MVHP_OUT_RGB}) {
+                            g_watch_hits = 0;
+                            CheckG c2;
+                            EXPECT(run_ex(req.flags & MVHP_OUTPUT_BOX ? "trim box" : "trim", o, s3, order, mask, req, c2, st) == MVHP_SUCCESS);
+                            EXPECT(c2.bad == 0 && c2.ok == cc.ok && c2.with_geometry == c2.ok && g_watch_hits >= 1);
+                            EXPECT(st.d2h_bytes == d2h_expected(s3, order, req, mask));
+                        }
+                    }
+                    {   // and probing a trimmed call: the boxes are those of the trimmed rectangle
+                        mvhp_output_request_t req = trim;
+                        CheckB cb;
+                        EXPECT(run_bars("trim and bars", o, 0, req, cb, st) == MVHP_SUCCESS && cb.bad == 0 && cb.ok == cc.ok);
+                    }
+                    EXPECT(mvhp_stream_set_trim(&s3, nullptr) == MVHP_SUCCESS);
+                }
+                for (auto &w : g_watch_crop) w = 0;
+            }
+            {   // minivideo_decode under MINIVIDEO_TRIM=1 on the stub device: the probe call, then the decode call, on one engine; and
+                // the malformed switches: FAILURE, with a message, before the device is touched
+                char tmpl[] = "/tmp/mvharness_XXXXXX";
+                const char *dir = mkdtemp(tmpl);
+                char cwd[4096];
+                EXPECT(dir != nullptr && getcwd(cwd, sizeof(cwd)) != nullptr);
+                std::string in = argv[4];
+                if (in[0] != '/') in = std::string(cwd) + "/" + in;
+                EXPECT(dir && chdir(dir) == 0);
+                setenv("MINIVIDEO_TRIM", "1", 1);
+                setenv("MINIVIDEO_TRIM_LEVEL", "40", 1);
+                for (const char *probes : {"1", "3", "64"}) {
+                    setenv("MINIVIDEO_TRIM_PROBES", probes, 1);
+                    MediaFile_t *m = nullptr;
+                    EXPECT(minivideo_open(in.c_str(), &m) == SUCCESS);
+                    EXPECT(m && minivideo_parse(m, false, true, false) == SUCCESS);
+                    const int calls0 = g_bars_calls;
+                    const int num = 5;
+                    EXPECT(m && minivideo_decode(m, ".", PICTURE_YUV420, 75, num, PICTURE_UNFILTERED) == SUCCESS);
+                    EXPECT(g_bars_calls > calls0 && g_bars_level == 40);
+                    int good = 0;
+                    for (int k = 0; k < num; k++) {
+                        const std::string name = std::string(m->file_name) + "_" + std::to_string(k) + ".yuv";
+                        const std::vector<uint8_t> f = read_file(name);
+                        remove(name.c_str());
+                        uint64_t got = 0;
+                        if (f.size() >= 8) memcpy(&got, f.data(), 8);
+                        if (got == picture_checksum(s3, k)) good++;
+                    }
+                    printf("%-28s probes=%s right picture in %d files\n", "public API, black bars", probes, good);
+                    EXPECT(good == num);
+                    EXPECT(minivideo_close(&m) == SUCCESS);
+                }
+                unsetenv("MINIVIDEO_TRIM_LEVEL"); unsetenv("MINIVIDEO_TRIM_PROBES");
+                struct Bad { const char *var, *value; };
+                for (const Bad &b : {Bad{"MINIVIDEO_TRIM_LEVEL", "300"}, Bad{"MINIVIDEO_TRIM_LEVEL", "0"}, Bad{"MINIVIDEO_TRIM_LEVEL", "255"},
+                                     Bad{"MINIVIDEO_TRIM_PROBES", "0"}, Bad{"MINIVIDEO_TRIM_PROBES", "65"}, Bad{"MINIVIDEO_TRIM", "x"}}) {
+                    setenv("MINIVIDEO_TRIM", "1", 1);
+                    setenv(b.var, b.value, 1);
+                    MediaFile_t *m = nullptr;
+                    EXPECT(minivideo_open(in.c_str(), &m) == SUCCESS);
+                    EXPECT(m && minivideo_parse(m, false, true, false) == SUCCESS);
+                    const int ctx_before = g_ctx_created, launches_before = g_recon_calls + g_geometry_calls + g_bars_calls;
+                    fflush(stdout);
+                    fflush(stderr);
+                    int pipefd[2];
+                    EXPECT(pipe(pipefd) == 0);
+                    const int saved = dup(2);
+                    dup2(pipefd[1], 2);
+                    const int rc = m ? minivideo_decode(m, ".", PICTURE_YUV420, 75, n3, PICTURE_UNFILTERED) : SUCCESS;
+                    fflush(stderr);
+                    dup2(saved, 2);
+                    close(saved);
+                    close(pipefd[1]);
+                    char msg[512] = "";
+                    const ssize_t got = read(pipefd[0], msg, sizeof(msg) - 1);
+                    close(pipefd[0]);
+                    printf("%-28s %s='%s' rc=%d message: %s", "malformed trim switch", b.var, b.value, rc, got > 0 ? msg : "(none)\n");
+                    EXPECT(rc == FAILURE && got > 0 && strstr(msg, b.var) != nullptr);
+                    EXPECT(g_ctx_created == ctx_before && g_recon_calls + g_geometry_calls + g_bars_calls == launches_before);
+                    EXPECT(minivideo_close(&m) == SUCCESS);
+                    unsetenv(b.var);
+                }
+                unsetenv("MINIVIDEO_TRIM");
+                EXPECT(chdir(cwd) == 0);
+                rmdir(dir);
+            }
+            printf("BARS MODE DONE\n");
         }
     }
     EXPECT(g_live_ctx == 0 && g_dev_allocs == 0);
