@@ -77,6 +77,24 @@
  *     devices.  Cost: the probes are entropy-decoded twice, at most MINIVIDEO_TRIM_PROBES pictures per call.  0 and the empty
  *     string for MINIVIDEO_TRIM are the files without the switch; a malformed value of any of the three variables is not
  *     ignored: minivideo_decode() returns FAILURE with a message before any device work;
+ *   - opt-in, outside the reference's behaviour and independent of the switches above: MINIVIDEO_REPRESENTATIVE=1 lets every
+ *     file hold a representative picture instead of whatever IDR picture the selection lands on (a title card, a flash
+ *     frame).  First every picture is written as without the switch, under the same names, and the GPU counts the histograms
+ *     of its luma and chroma samples (of the SPS's cropped rectangle where a switch above crops, else of the coded picture).
+ *     Then up to MINIVIDEO_REPRESENTATIVE_ALTERNATES (1 ... 16, default 8) of the IDR pictures between each file's picture
+ *     and the next selected one (to the end of the stream behind the last one) are decoded for their histograms alone, and
+ *     each file's candidates -- its picture first, then its alternates in stream order, those of another size left out --
+ *     are compared: the one nearest the candidates' mean histogram wins (sum over the 768 bins of the three planes of the
+ *     squared difference, in integers; the earliest on a tie, so one or two candidates keep the file as it is).  Last, the
+ *     winners that are not already in their files are decoded once more with all the switches of the call, written to
+ *     <name>.part and renamed over the files: if that write fails, the file keeps the picture it had.  With
+ *     MINIVIDEO_SKIP_BLANK=1 as well the two run as one: only candidates that are not blank (the score is taken from the
+ *     histogram, the threshold is MINIVIDEO_BLANK_VARIANCE) are compared, a file whose candidates are all blank gets the
+ *     highest-scoring one, and MINIVIDEO_BLANK_ALTERNATES is not read.  The number of files, their names, the return value
+ *     and picture_number mean what they mean without the switch, and the files do not depend on batch sizes, threads or
+ *     devices.  Cost: every alternate is entropy-decoded and reconstructed, up to MINIVIDEO_REPRESENTATIVE_ALTERNATES + 1
+ *     times the work per file.  A malformed value of either variable is not ignored: minivideo_decode() returns FAILURE with
+ *     a message before any device work;
  *   - H.264 IDR pictures only, from Annex-B elementary streams (.264/.h264 or a
  *     file starting with an SPS start code) or from the first H.264 video track
  *     of an MP4/MOV file (demuxer/mp4/mp4.c:1950 mp4_fileParse -> sync samples).

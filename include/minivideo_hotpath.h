@@ -346,6 +346,14 @@ typedef struct mvhp_output_geometry {
 #define MVHP_OUTPUT_BARS 0x1000u
 #define MVHP_OUTPUT_TRIM 0x2000u
 #define MVHP_BARS_REQUEST(level) (((uint32_t)(level) & 0xffu) << 24)
+/* Representative pictures (opt-in; "Representative pictures" below).  MVHP_OUTPUT_HIST (mvhp_engine_decode_ex only) probes: behind
+ * whatever reconstructs the batch (and the deblocking filter) mvhp_plane_hist_dev runs over each picture's crop rectangle on the
+ * coded planes, the 3104-byte records come back with the pictures, and the sink reads its picture's record with
+ * mvhp_engine_picture_hist (the sink's signature and g->reserved[] stay as they are).  The flag changes no picture: a request with
+ * this flag alone still means pictures of the coded size; d2h_bytes grows by exactly 3104 per delivered picture of a downloaded
+ * batch.  It composes with every other flag, MVHP_OUTPUT_SCORE included, and every output kind, except MVHP_OUTPUT_BARS: two
+ * probes in one call are refused. */
+#define MVHP_OUTPUT_HIST 0x4000u
 typedef struct mvhp_output_request {
     uint32_t flags;           /* MVHP_OUTPUT_*; 0 = the coded size (what the reference writes)                  */
     uint32_t box_w, box_h;
@@ -606,6 +614,38 @@ MVHP_EXPORT int      mvhp_stream_trim(const mvhp_stream_t *s, mvhp_luma_bars_t *
 MVHP_EXPORT int      mvhp_luma_bars_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
                                         const uint8_t *d_yuv_coded, int n, int level, mvhp_luma_bars_t *d_bars, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Representative pictures (opt-in; DESIGN.md 3 "Representative pictures"): the histograms of the three planes of a picture's
+ * rectangle, counted on the device, so that a caller can keep, among a handful of candidates, the one that looks most like all
+ * of them (minivideo_decode does under MINIVIDEO_REPRESENTATIVE=1, include/minivideo.h).  The device counts; the choice is
+ * integer arithmetic on the host.
+ * ------------------------------------------------------------------------- */
+typedef struct mvhp_plane_hist {   /* 3104 bytes, 16-byte aligned */
+    uint32_t y[256], cb[256], cr[256];   /* counts of the samples of the rectangle, per value */
+    uint32_t samples;                    /* crop_w * crop_h (<= 2^28)                          */
+    uint32_t chroma_samples;             /* (crop_w / 2) * (crop_h / 2)                        */
+    uint32_t reserved[6];                /* 0                                                  */
+} mvhp_plane_hist_t;
+/* The picture-score record of the same rectangle, from the luma histogram: sum = sum of v y[v], sumsq = sum of v^2 y[v],
+ * samples = sum of y[v], reserved = 0 -- the 32 bytes mvhp_luma_stats_dev writes for that rectangle, so mvhp_luma_score of it is
+ * the picture's blank score and one probe serves both features.  A host function. */
+MVHP_EXPORT int      mvhp_hist_stats(const mvhp_plane_hist_t *h, mvhp_luma_stats_t *out);
+/* The candidate that looks most like all of them.  The candidates are the entries of h[0..n) that are eligible (eligible[i] != 0;
+ * NULL = all) and whose samples and chroma_samples equal those of the first eligible entry (entry 0, the primary, when it is
+ * eligible).  With k candidates and M[b] the sum of their counts in bin b, over all 768 bins of the three planes,
+ * D_i = sum over b of (k h_i[b] - M[b])^2 -- k^2 times the squared distance to the mean histogram, in 128-bit integers (counts up
+ * to 2^28 and k up to 17 stay far inside them) -- and the function returns the index of the smallest D, the earliest on a tie: the
+ * first candidate for k = 1 and k = 2.  No eligible entry, n <= 0 or h == NULL: -1.  A host function. */
+MVHP_EXPORT int      mvhp_represent_choose(const mvhp_plane_hist_t *h, int n, const uint8_t *eligible);
+/* n coded pictures (d_yuv_coded: mvhp_yuv_frame_bytes(p) apart, 16-byte aligned, luma pitch 16 W, chroma pitch 8 W) -> n records
+ * in d_hist (16-byte aligned): y over the luma rectangle crop_x, crop_y, crop_w, crop_h of g (all even, inside the coded picture,
+ * at least 2 x 2; out_w / out_h are not read), cb and cr over the same rectangle halved.  n = 0 does nothing; n < 0, a rectangle
+ * outside the picture, odd or zero sizes and NULL or misaligned pointers are refused (MVHP_FAILURE) before anything is launched.
+ * Asynchronous on `stream` (NULL = the context's own); the call zeroes the records on that stream itself.  Nothing survives a
+ * launch and no kernel waits: safe under stream capture, and two calls on two streams do not meet. */
+MVHP_EXPORT int      mvhp_plane_hist_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                                         const uint8_t *d_yuv_coded, int n, mvhp_plane_hist_t *d_hist, void *stream);
+
 /* Page-locked host memory for the host-buffer entry points (H2D / D2H at full PCIe rate). */
 MVHP_EXPORT void *mvhp_host_alloc(size_t bytes);
 MVHP_EXPORT void  mvhp_host_free(void *p);
@@ -659,6 +699,11 @@ MVHP_EXPORT int  mvhp_set_stats_band(mvhp_ctx_t *ctx, int rows);
  * short ones where the grid would leave compute units idle).  It exists so that a test can force band sizes and compare the
  * records: the counts are integers, every value gives the same 32 bytes. */
 MVHP_EXPORT int  mvhp_set_bars_band(mvhp_ctx_t *ctx, int rows);
+
+/* Test-only knob, like the two above (speed only, never results; not meant for products): luma rows per workgroup of
+ * mvhp_plane_hist_dev, 1 ... 65536; 0 (default) = 256, fewer when the grid would leave compute units idle.  It exists so that a
+ * test can force band sizes and compare the records: the counts are integers, every value gives the same 3104 bytes. */
+MVHP_EXPORT int  mvhp_set_hist_band(mvhp_ctx_t *ctx, int rows);
 
 /* Tuning knob (speed only, never results): waves per picture workgroup, or macroblock rows per band of the banded forms
  * (1, 2, 4, 6, 8, 12 or 16; a layout that is not built for the value takes the next smaller one it is built for, or its
@@ -815,6 +860,9 @@ MVHP_EXPORT int  mvhp_engine_decode_ex(mvhp_engine_t *e, const mvhp_stream_t *s,
                                        mvhp_decode_stats_t *stats);
 /* Gives back a picture the sink kept (verdict 2) during the running mvhp_engine_decode call; anything else is ignored. */
 MVHP_EXPORT void mvhp_engine_release_picture(mvhp_engine_t *e, int seq);
+/* MVHP_OUTPUT_HIST: the record of picture `seq` of the running call.  Valid inside the sink call for `seq`, and for a picture the
+ * sink kept (verdict 2) until mvhp_engine_release_picture; NULL without the flag, for a failed picture and at any other time. */
+MVHP_EXPORT const mvhp_plane_hist_t *mvhp_engine_picture_hist(mvhp_engine_t *e, int seq);
 
 /* ---- memory placement (MI355X: device memory alternates, in regions of tens of GB, between two halves of the memory
  * system; DESIGN.md 3 "Placement") ---- */

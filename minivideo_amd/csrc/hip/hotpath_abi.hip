@@ -17,6 +17,7 @@
 #include "minivideo_hotpath.h"
 #include "png_format.h"
 #include "recon_kernels.h"
+#include "represent_policy.h"
 
 namespace {
 
@@ -62,6 +63,7 @@ struct mvhp_ctx {
     int          crop_copy;   // 1 = crop-only geometries run the copy kernel (crop_copy.hip), 0 = the general resample kernel
     int          stats_band;  // luma rows per workgroup of the picture-score kernel, 0 = choose (mvhp_set_stats_band)
     int          bars_band;   // luma rows per workgroup of the black-bar counting pass, 0 = choose (mvhp_set_bars_band)
+    int          hist_band;   // luma rows per workgroup of the plane-histogram kernel, 0 = choose (mvhp_set_hist_band)
     int          n_cus;
     size_t       max_lds;
     int          last_layout, last_waves;   // what the last reconstruction launch used
@@ -243,6 +245,13 @@ MVHP_EXPORT int mvhp_set_bars_band(mvhp_ctx_t *c, int rows)
 {
     if (!c || rows < 0 || rows > 65536) return MVHP_FAILURE;
     c->bars_band = rows;
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT int mvhp_set_hist_band(mvhp_ctx_t *c, int rows)
+{
+    if (!c || rows < 0 || rows > 65536) return MVHP_FAILURE;
+    c->hist_band = rows;
     return MVHP_SUCCESS;
 }
 
@@ -678,6 +687,51 @@ MVHP_EXPORT int mvhp_luma_bars_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p,
     return MVHP_SUCCESS;
 }
 
+MVHP_EXPORT int mvhp_hist_stats(const mvhp_plane_hist_t *h, mvhp_luma_stats_t *out)
+{
+    if (!h || !out) return MVHP_FAILURE;
+    mvrep::hist_stats(*h, *out);
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT int mvhp_represent_choose(const mvhp_plane_hist_t *h, int n, const uint8_t *eligible) { return mvrep::choose(h, n, eligible); }
+
+MVHP_EXPORT int mvhp_plane_hist_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                                    const uint8_t *d_yuv_coded, int n, mvhp_plane_hist_t *d_hist, void *stream)
+{
+    if (!c || !params_ok(p) || !g || !d_yuv_coded || n < 0 || ((uintptr_t)d_yuv_coded & 15) || !d_hist || ((uintptr_t)d_hist & 15)) {
+        set_err("mvhp_plane_hist_dev: invalid argument");
+        return MVHP_FAILURE;
+    }
+    const uint32_t Wp = p->width_mbs * 16, Hp = p->height_mbs * 16;
+    if (((g->crop_x | g->crop_y | g->crop_w | g->crop_h) & 1u) || g->crop_w < 2 || g->crop_h < 2 || g->crop_x > Wp ||
+        g->crop_w > Wp - g->crop_x || g->crop_y > Hp || g->crop_h > Hp - g->crop_y) {
+        set_err("mvhp_plane_hist_dev: rectangle %u,%u %ux%u of a %ux%u picture (even offsets and sizes of at least 2, inside the picture)",
+                g->crop_x, g->crop_y, g->crop_w, g->crop_h, Wp, Hp);
+        return MVHP_FAILURE;
+    }
+    // (a coded picture has at most 2^28 samples: `samples`, every count and the choice's arithmetic are sized for that)
+    if (n == 0) return MVHP_SUCCESS;
+    HIP_TRY(hipSetDevice(c->device));
+    mvhp::PlaneHistArgs a;
+    a.src = d_yuv_coded;
+    a.frame_bytes = mvhp_yuv_frame_bytes(p);
+    a.n = n;
+    a.pitch = (int)Wp;
+    a.rows = (int)Hp;
+    a.cx = (int)g->crop_x; a.cy = (int)g->crop_y; a.cw = (int)g->crop_w; a.ch = (int)g->crop_h;
+    // luma rows per workgroup: a workgroup zeroes and sums 48 KiB of LDS and issues up to 768 atomic adds whatever its band, so
+    // bands are tall (256 rows: 1080p in five; measured against 16 ... 1080 rows, DESIGN.md 3 "Representative pictures"), halved
+    // while the grid would leave CUs idle -- the rule of the crop copy above.  Speed only: the counts are integers, any band size
+    // gives the same record.
+    int band = c->hist_band > 0 ? c->hist_band : 256;
+    while (c->hist_band <= 0 && band > 1 && (double)n * ((a.ch + band - 1) / band) < 4.0 * c->n_cus) band /= 2;
+    a.band = band;
+    a.hist = d_hist;
+    HIP_TRY(mvhp::launch_plane_hist(a, stream_of(c, stream)));
+    return MVHP_SUCCESS;
+}
+
 MVHP_EXPORT size_t mvhp_jpeg_header_bytes(void) { return MVHP_JPEG_HEADER_BYTES; }
 
 MVHP_EXPORT int mvhp_jpeg_quant_tables(int quality, uint8_t out[128])
@@ -1054,6 +1108,12 @@ int eng_run_batch(DevCtx *d, const mvengine::BatchJob &j, mvengine::BatchDone &d
         whole.crop_h = whole.out_h = p->height_mbs * 16;
         rc = mvhp_luma_bars_dev(c, p, j.geom ? j.geom : &whole, j.d_yuv, j.n, j.bars_level, j.bars, c->stream);
     }
+    if (rc == MVHP_SUCCESS && j.hist) {
+        mvhp_output_geometry_t whole{};
+        whole.crop_w = whole.out_w = p->width_mbs * 16;
+        whole.crop_h = whole.out_h = p->height_mbs * 16;
+        rc = mvhp_plane_hist_dev(c, p, j.geom ? j.geom : &whole, j.d_yuv, j.n, j.hist, c->stream);
+    }
     if (rc != MVHP_SUCCESS) { err = mvhp_last_error(); return rc; }
     ENG_TRY(hipEventRecord(d->ev[3], c->stream));
     std::string ew;
@@ -1106,7 +1166,7 @@ void eng_placed_free(DevCtx *d, void *arena)
 
 const mvengine::DeviceApi g_hip_api = {
     mvhp_device_count, mvhp_host_alloc, mvhp_host_free, eng_ctx_create, eng_ctx_destroy, eng_dev_alloc, eng_dev_free,
-    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_COLOR | mvengine::CAP_PNG | mvengine::CAP_BARS,
+    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_COLOR | mvengine::CAP_PNG | mvengine::CAP_BARS | mvengine::CAP_HIST,
     eng_placed_alloc, eng_placed_free,
 };
 

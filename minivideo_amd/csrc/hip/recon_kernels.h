@@ -196,4 +196,17 @@ struct LumaBarsArgs {
 size_t     luma_bars_scratch_bytes(const LumaBarsArgs &a);
 hipError_t launch_luma_bars(const LumaBarsArgs &a, hipStream_t stream);
 
+// representative pictures (plane_hist.hip): the histograms of the three planes over one rectangle of every picture
+struct PlaneHistArgs {
+    const uint8_t     *src;          // n coded pictures, 16-byte aligned
+    size_t             frame_bytes;  // from one picture to the next (a multiple of 16)
+    int                n;
+    int                pitch;        // of the luma plane, a multiple of 16 (the chroma planes: half of it)
+    int                rows;         // of the luma plane (the chroma planes follow it: Cb at pitch * rows, Cr a quarter further)
+    int                cx, cy, cw, ch;   // the luma rectangle, inside the picture, all even, cw and ch at least 2
+    int                band;         // luma rows per workgroup
+    mvhp_plane_hist_t *hist;         // n records, 16-byte aligned
+};
+hipError_t launch_plane_hist(const PlaneHistArgs &a, hipStream_t stream);
+
 } // namespace mvhp

@@ -29,6 +29,7 @@
 #include "decode_engine.h"
 #include "bars_policy.h"
 #include "blank_policy.h"
+#include "represent_policy.h"
 #include "export.h"
 #include "h264_frontend.h"
 #include "minivideo.h"
@@ -344,6 +345,21 @@ struct ExportSink {
     // MINIVIDEO_SKIP_BLANK=1: what each slot (the _k of the file name) holds after pass 1 -- its IDR, its score, its file
     struct Slot { int idr; uint32_t score; std::string name; };
     std::vector<Slot> *slots = nullptr;
+    // MINIVIDEO_REPRESENTATIVE=1: the plane histograms of the slots' pictures, one per entry of `slots` (MVHP_OUTPUT_HIST); the
+    // slot's score is then the histogram's own (mvhp_hist_stats), not g->reserved[1]
+    std::vector<mvhp_plane_hist_t> *hists = nullptr;
+    void note_slot(int seq, int idr, uint32_t score, const std::string &name)
+    {
+        if (!slots) return;
+        if (hists) {
+            const mvhp_plane_hist_t *h = mvhp_engine_picture_hist(eng, seq);
+            hists->push_back(h ? *h : mvhp_plane_hist_t{});
+            mvhp_luma_stats_t st;
+            mvrep::hist_stats(hists->back(), st);
+            score = mvblank::luma_score(st.sum, st.sumsq, st.samples);
+        }
+        slots->push_back(Slot{idr, score, name});
+    }
 
     bool png_dev = false;           // MINIVIDEO_PNG=1 and fmt == PICTURE_PNG: the files are made on the device (MVHP_OUT_PNG)
     bool device_file() const { return fmt == PICTURE_JPG || png_dev; }
@@ -421,7 +437,7 @@ struct ExportSink {
         const int W = (int)g->out_w, H = (int)g->out_h;   // the coded size unless MINIVIDEO_CROP / MINIVIDEO_THUMBNAIL ask for less
         const size_t file_bytes = x.device_file() ? g->reserved[0] : 0;   // (MVHP_OUT_JPEG / _PNG: the length of the file in `rgb`)
         if (!x.pool.empty()) {
-            if (x.write_errors.load() == 0 && x.slots) x.slots->push_back(Slot{idr, g->reserved[1], name});
+            if (x.write_errors.load() == 0) x.note_slot(seq, idr, g->reserved[1], name);
             // Writers run behind the pipeline, so a write that fails is only known later: no further picture is decoded in
             // its place (the synchronous path below does that).  Once one has failed -- a full disk does not get better --
             // decoding stops, and minivideo_decode answers FAILURE unless every wanted file was written (contract: minivideo.h).
@@ -441,7 +457,7 @@ struct ExportSink {
             x.errors++;
             return 0;
         }
-        if (x.slots) x.slots->push_back(Slot{idr, g->reserved[1], name});
+        x.note_slot(seq, idr, g->reserved[1], name);
         x.exported++;
         x.written++;
         return 1;
@@ -491,6 +507,61 @@ struct AlternateSink {
         }
         slot.idr = idr;
         slot.score = g->reserved[1];
+        a.replaced++;
+        return 1;
+    }
+};
+
+// ---- MINIVIDEO_REPRESENTATIVE=1 (include/minivideo.h; DESIGN.md 3 "Representative pictures") ----
+// pass 2: the alternates of every slot, decoded for their histograms alone; the planes that come with them are not looked at
+struct HistSink {
+    mvhp_engine_t *eng = nullptr;
+    std::vector<mvhp_plane_hist_t> hists;   // per picture of pass 2's order
+    std::vector<uint8_t> have;              // ... and whether it arrived: a failed alternate is skipped
+    int decoded = 0;
+
+    static int call(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *, const mvhp_output_geometry_t *,
+                    const uint8_t *, const uint8_t *)
+    {
+        HistSink &a = *static_cast<HistSink *>(user);
+        const mvhp_plane_hist_t *h = rc == MVHP_SUCCESS ? mvhp_engine_picture_hist(a.eng, seq) : nullptr;
+        if (!h) {
+            log_err("IDR %d: %s", idr, err && *err ? err : "failed");
+            return 0;
+        }
+        a.hists[(size_t)seq] = *h;
+        a.have[(size_t)seq] = 1;
+        a.decoded++;
+        return 1;
+    }
+};
+
+// pass 3: the winners that are not their slot's primary, decoded with the request and the output kind of pass 1; each file is
+// written beside the slot's file and renamed over it, on the calling thread, as AlternateSink does
+struct ReplaceSink {
+    ExportSink *x = nullptr;
+    std::vector<ExportSink::Slot> *slots = nullptr;
+    std::vector<int> slot_of;               // per picture of pass 3's order: its slot
+    int replaced = 0;
+
+    static int call(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *, const mvhp_output_geometry_t *g,
+                    const uint8_t *yuv, const uint8_t *rgb)
+    {
+        ReplaceSink &a = *static_cast<ReplaceSink *>(user);
+        ExportSink &x = *a.x;
+        if (rc != MVHP_SUCCESS) {   // the slot keeps its primary
+            log_err("IDR %d: %s", idr, err && *err ? err : "failed");
+            return 0;
+        }
+        ExportSink::Slot &slot = (*a.slots)[(size_t)a.slot_of[(size_t)seq]];
+        const size_t file_bytes = x.device_file() ? g->reserved[0] : 0;
+        const std::string part = slot.name + ".part";   // (a write that fails leaves the earlier file whole)
+        if (!x.write_one(part, (int)g->out_w, (int)g->out_h, yuv, rgb, file_bytes) || rename(part.c_str(), slot.name.c_str()) != 0) {
+            log_err("Unable to write '%s'", slot.name.c_str());
+            (void)unlink(part.c_str());
+            return 0;
+        }
+        slot.idr = idr;
         a.replaced++;
         return 1;
     }
@@ -624,6 +695,14 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
         if (!mvblank::settings_from(getenv("MINIVIDEO_SKIP_BLANK"), getenv("MINIVIDEO_BLANK_VARIANCE"),
                                     getenv("MINIVIDEO_BLANK_ALTERNATES"), blank, why)) { log_err("%s", why.c_str()); return FAILURE; }
     }
+    mvrep::Settings represent;
+    {   // and for the representative-picture switches
+        std::string why;
+        if (!mvrep::settings_from(getenv("MINIVIDEO_REPRESENTATIVE"), getenv("MINIVIDEO_REPRESENTATIVE_ALTERNATES"), represent, why)) {
+            log_err("%s", why.c_str());
+            return FAILURE;
+        }
+    }
     mvbars::Settings trim;
     {   // and for the black-bar switches
         std::string why;
@@ -707,6 +786,7 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     sink.want_rgb = want_rgb;
     sink.png_dev = png_dev;
     sink.picture_number = picture_number;
+    sink.eng = eng;
     {   // file writers: two per sixteen cores keep up with the pipeline on the raw formats (0.5 ms of copying per picture);
         // the entropy threads need the rest.  PNG and TGA cost more CPU per picture than entropy decoding does (two checksums
         // over 6.3 MB, 7 ms; the run-length coder, 5 ms; against 3.7 ms): half as many writers as cores -- they sleep when
@@ -728,7 +808,11 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     if (jpeg) req.reserved = MVHP_JPEG_REQUEST(std::min(100, std::max(1, picture_quality)), 0);
     // opt-in (MINIVIDEO_SKIP_BLANK=1, outside the parity contract): the same call with every picture's score, pass 1 of 2
     std::vector<ExportSink::Slot> slots;
-    if (blank.on) { req.flags |= MVHP_OUTPUT_SCORE; sink.slots = &slots; }
+    // opt-in (MINIVIDEO_REPRESENTATIVE=1, outside the parity contract): the same call with every picture's plane histograms, pass 1
+    // of 3.  With both switches the histograms serve both: their own score is the blank score, and blank skipping's pass is not run
+    std::vector<mvhp_plane_hist_t> hists;
+    if (represent.on) { req.flags |= MVHP_OUTPUT_HIST; sink.slots = &slots; sink.hists = &hists; }
+    else if (blank.on) { req.flags |= MVHP_OUTPUT_SCORE; sink.slots = &slots; }
     const int out_kind = jpeg ? MVHP_OUT_JPEG : png_dev ? MVHP_OUT_PNG : want_rgb ? MVHP_OUT_RGB_ONLY : 0;
     if (trim.on) {
         // opt-in (MINIVIDEO_TRIM=1, outside the parity contract): black bars are a property of the stream, so a few pictures of
@@ -776,7 +860,75 @@ minivideo_EXPORT int minivideo_decode(MediaFile_t *m, const char *output_directo
     (void)mvhp_engine_decode_ex(eng, &s, order.data(), (int)order.size(), wanted, out_kind,
                                 (req.flags || jpeg) ? &req : nullptr, ExportSink::call, &sink, &st);   // (MVHP_OUT_PNG has no parameters)
     sink.finish();   // (every kept picture is back: mvhp_engine_decode waits for that)
-    if (blank.on && !sink.aborted && sink.write_errors.load() == 0) {
+    if (represent.on && !sink.aborted && sink.write_errors.load() == 0 && hists.size() == slots.size()) {
+        // pass 2: the alternates of every slot -- the IDRs strictly between its picture and the next slot's, at most
+        // MINIVIDEO_REPRESENTATIVE_ALTERNATES -- in one call that asks for planes of the rectangle pass 1 counted over (the crop
+        // where pass 1 crops, trims, scales or squares; no box, turn, colour or file coding) and keeps only the histograms.
+        // Slots, alternates, histograms and the choice are functions of the stream and the switches alone: the files do not
+        // depend on batch sizes, threads or contexts.
+        std::vector<int> idrs, order2, first_of;   // first_of[k]: where slot k's alternates start in order2
+        for (const ExportSink::Slot &sl : slots) idrs.push_back(sl.idr);
+        for (int k = 0; k < (int)slots.size(); k++) {
+            first_of.push_back((int)order2.size());
+            for (int i : mvblank::alternates(idrs, (int)s.idrs.size(), represent.alternates, k)) order2.push_back(i);
+        }
+        first_of.push_back((int)order2.size());
+        HistSink hs;
+        hs.eng = eng;
+        hs.hists.resize(order2.size());
+        hs.have.assign(order2.size(), 0);
+        mvhp_decode_stats_t st2, st3;
+        memset(&st2, 0, sizeof(st2));
+        memset(&st3, 0, sizeof(st3));
+        if (!order2.empty()) {
+            mvhp_output_request_t req2{};
+            req2.flags = MVHP_OUTPUT_HIST | (req.flags & MVHP_OUTPUT_TRIM);
+            if (req.flags & (MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_ASPECT | MVHP_OUTPUT_TRIM)) req2.flags |= MVHP_OUTPUT_CROP;
+            (void)mvhp_engine_decode_ex(eng, &s, order2.data(), (int)order2.size(), (int)order2.size(), 0, &req2, HistSink::call, &hs, &st2);
+        }
+        // the choice, per slot: the primary first, then the alternates that arrived.  With MINIVIDEO_SKIP_BLANK=1 a candidate is
+        // eligible when its score reaches the threshold; a slot without an eligible candidate goes to the blank policy's rule.
+        ReplaceSink rs;
+        rs.x = &sink;
+        rs.slots = &slots;
+        std::vector<int> order3;
+        for (int k = 0; k < (int)slots.size() && !order2.empty(); k++) {
+            std::vector<mvhp_plane_hist_t> cand{hists[(size_t)k]};
+            std::vector<int> cand_idr{slots[(size_t)k].idr};
+            for (int i = first_of[(size_t)k]; i < first_of[(size_t)k + 1]; i++)
+                if (hs.have[(size_t)i]) { cand.push_back(hs.hists[(size_t)i]); cand_idr.push_back(order2[(size_t)i]); }
+            if (cand.size() < 2) continue;
+            std::vector<uint8_t> eligible;
+            std::vector<uint32_t> scores;
+            for (const mvhp_plane_hist_t &h : cand) {
+                mvhp_luma_stats_t ls;
+                mvrep::hist_stats(h, ls);
+                scores.push_back(mvblank::luma_score(ls.sum, ls.sumsq, ls.samples));
+                eligible.push_back(scores.back() >= blank.min_score ? 1 : 0);
+            }
+            int w = mvrep::choose(cand.data(), (int)cand.size(), blank.on ? eligible.data() : nullptr);
+            if (w < 0) w = mvblank::choose(scores.data(), (int)scores.size(), blank.min_score);
+            if (w > 0) { order3.push_back(cand_idr[(size_t)w]); rs.slot_of.push_back(k); }
+        }
+        // pass 3: the winners that are not primaries, with the request and the output kind of pass 1, written over the slots' files
+        if (!order3.empty()) {
+            mvhp_output_request_t req3 = req;
+            req3.flags &= ~MVHP_OUTPUT_HIST;
+            (void)mvhp_engine_decode_ex(eng, &s, order3.data(), (int)order3.size(), (int)order3.size(), out_kind,
+                                        (req3.flags || jpeg) ? &req3 : nullptr, ReplaceSink::call, &rs, &st3);
+        }
+        if (getenv("MINIVIDEO_STATS")) {
+            std::string l2, l3;
+            for (int i : order2) l2 += " " + std::to_string(i);
+            for (int i : order3) l3 += " " + std::to_string(i);
+            fprintf(stderr, "[minivideo] representative pictures: %d slots, %d candidates listed, %d decoded, %d files replaced, "
+                            "pass 2 %.3f s (%u entropy-decoded), pass 3 %.3f s (%u entropy-decoded)\n", (int)slots.size(), (int)order2.size(),
+                    hs.decoded, rs.replaced, st2.wall_s, st2.pictures_issued, st3.wall_s, st3.pictures_issued);
+            fprintf(stderr, "[minivideo] representative pictures: pass 2 order:%s; pass 3 order:%s\n", l2.empty() ? " none" : l2.c_str(),
+                    l3.empty() ? " none" : l3.c_str());
+        }
+    }
+    if (blank.on && !represent.on && !sink.aborted && sink.write_errors.load() == 0) {
         // pass 2: the alternates of every slot whose picture scores below the threshold -- the IDRs between it and the next
         // slot's picture (select_idrs' size filter does not apply to them).  Slots, scores and alternates are functions of
         // the stream and the switches alone, and the sink sees pictures in the order of the list: the files do not depend on

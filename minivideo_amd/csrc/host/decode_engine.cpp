@@ -122,6 +122,7 @@ struct OutChunk {
     Pinned yuv, rgb;         // (MVHP_OUT_JPEG, MVHP_OUT_PNG: rgb holds the files of the chunk's pictures, tab their table entries)
     Pinned tab;
     Pinned stats;            // (MVHP_OUTPUT_SCORE: the records of the chunk's pictures)
+    Pinned hist;             // (MVHP_OUTPUT_HIST: the histograms of the chunk's pictures)
     int refs = 0;            // pictures handed to the sink queue and not yet consumed
 };
 
@@ -133,6 +134,7 @@ struct PicResult {
     mvhp_output_geometry_t geom{};   // what yuv / rgb hold (the coded size unless the call has an output request)
     OutChunk *oc = nullptr;
     const uint8_t *yuv = nullptr, *rgb = nullptr;
+    const mvhp_plane_hist_t *hist = nullptr;   // MVHP_OUTPUT_HIST: the picture's record in `oc` (picture_hist())
     bool ready = false;      // final: the sink may take it
     bool parsed_ok = false;
     bool kept = false;       // the sink answered 2: its output chunk stays referenced until release_picture()
@@ -151,6 +153,7 @@ enum BufKind {
     kJpegBlob,   // MVHP_OUT_JPEG: the encoder's blob (n x the raw picture); MVHP_OUT_PNG: n x the longest file ...
     kJpegTab,    // ... and table of a batch
     kStats,      // MVHP_OUTPUT_SCORE or MVHP_OUTPUT_BARS (never both): the records of a batch (n x 32 bytes)
+    kHist,       // MVHP_OUTPUT_HIST: the plane histograms of a batch (n x 3104 bytes)
     kBufKinds,
     kArenaKinds = kOutYuv,
 };
@@ -192,6 +195,7 @@ struct Wants {
                                     // final planes (which a batch with a geometry then keeps, whether or not they are downloaded)
     bool bars = false;              // MVHP_OUTPUT_BARS (it changes no picture and no path; never beside score, jpeg or png)
     int bars_level = MVHP_BARS_LEVEL_DEFAULT;
+    bool hist = false;              // MVHP_OUTPUT_HIST (it changes no picture and no path; never beside bars)
 };
 // whether a batch of the DELIVERED geometry g, turned by `turns`, has a resample pass in front of the turn
 bool scales_before_turn(const mvhp_output_geometry_t &g, int turns)
@@ -225,6 +229,7 @@ size_t picture_bytes(BufKind k, const mvhp_stream_params_t &p, const mvhp_output
     case kJpegBlob: return w.jpeg ? mvhp_geometry_yuv_bytes(&g) : w.png ? png_blob_bytes(g) : 0;
     case kJpegTab:  return w.jpeg || w.png ? sizeof(mvhp_jpeg_entry_t) : 0;
     case kStats:    return w.score ? sizeof(mvhp_luma_stats_t) : w.bars ? sizeof(mvhp_luma_bars_t) : 0;
+    case kHist:     return w.hist ? sizeof(mvhp_plane_hist_t) : 0;
     default:        return 0;
     }
 }
@@ -328,6 +333,7 @@ private:
     void put_out(OutChunk *oc);
 public:
     void release_picture(int seq);   // any thread
+    const mvhp_plane_hist_t *picture_hist(int seq);   // any thread
 private:
     bool grow(Pinned &p, size_t need);   // no lock needed
     int launch_cap(size_t per_picture) const;
@@ -389,7 +395,7 @@ private:
 Engine::~Engine()
 {
     for (auto &c : all_in_) api_.host_free(c->buf.p);
-    for (auto &c : all_out_) { api_.host_free(c->yuv.p); api_.host_free(c->rgb.p); api_.host_free(c->tab.p); api_.host_free(c->stats.p); }
+    for (auto &c : all_out_) { api_.host_free(c->yuv.p); api_.host_free(c->rgb.p); api_.host_free(c->tab.p); api_.host_free(c->stats.p); api_.host_free(c->hist.p); }
     for (Ctx &c : ctx_) {
         if (c.arena) {   // pieces of the arena go with it; a buffer that left the arena is freed below like any other
             for (DevBuf &b : c.bufs) if (b.arena_piece) b.leave_arena();
@@ -605,7 +611,7 @@ bool Engine::ensure_devbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
     static const struct { const char *of, *unit; } what[kBufKinds] = {
         {"", " pictures"}, {"", " pictures"}, {"", " pictures"}, {"", " pictures"}, {"the output pictures of ", ""}, {"the output pictures of ", ""},
         {"the unturned pictures of ", ""},
-        {"the JPEG files of ", ""}, {"the JPEG files of ", ""}, {"the picture scores of ", ""}};
+        {"the JPEG files of ", ""}, {"the JPEG files of ", ""}, {"the picture scores of ", ""}, {"the plane histograms of ", ""}};
     const bool job_shape = bt.params.width_mbs == job_params_.width_mbs && bt.params.height_mbs == job_params_.height_mbs;
     for (int k = 0; k < kBufKinds; k++) {
         if (k < kArenaKinds && b.arena_piece) continue;   // (checked above; never grown one by one)
@@ -1002,6 +1008,7 @@ void Engine::launcher(int k)
         if (inject) err = "injected failure (test hook)";
         else if (w_.score && !(api_.caps & CAP_SCORE)) err = "this device table has no picture-score operation";
         else if (w_.bars && !(api_.caps & CAP_BARS)) err = "this device table has no black-bar operation";
+        else if (w_.hist && !(api_.caps & CAP_HIST)) err = "this device table has no plane-histogram operation";
         else if (w_.jpeg && !(api_.caps & CAP_JPEG)) err = "this device table has no JPEG operation";
         else if (w_.png && !(api_.caps & CAP_PNG)) err = "this device table has no PNG operation";
         else if (b->use_geom && !w_.jpeg && !(api_.caps & CAP_GEOMETRY)) err = "this device table has no output-geometry operation";
@@ -1031,6 +1038,7 @@ void Engine::launcher(int k)
             job.stats = w_.score ? (mvhp_luma_stats_t *)buf(kStats) : nullptr;
             job.bars = w_.bars ? (mvhp_luma_bars_t *)buf(kStats) : nullptr;
             job.bars_level = w_.bars_level;
+            job.hist = w_.hist ? (mvhp_plane_hist_t *)buf(kHist) : nullptr;
             rc = api_.run_batch(cx.dev, job, done, err);
         }
         const float ms = done.ms;
@@ -1073,6 +1081,16 @@ void Engine::release_picture(int seq)
     cv_.notify_all();
 }
 
+const mvhp_plane_hist_t *Engine::picture_hist(int seq)
+{
+    std::lock_guard<std::mutex> l(mu_);
+    if (seq < 0 || (size_t)seq >= results_.size()) return nullptr;
+    const PicResult &r = results_[(size_t)seq];
+    // (inside the picture's sink call, or kept by it: its output chunk, which holds the record, is referenced)
+    if ((seq != in_sink_ && !r.kept) || r.rc != MVHP_SUCCESS || !r.oc) return nullptr;
+    return r.hist;
+}
+
 void Engine::put_out(OutChunk *oc)
 {
     free_out_.push_back(oc);
@@ -1093,7 +1111,8 @@ void Engine::downloader(int k)
         // what comes back, from where, how many bytes per picture (a batch with a geometry: only its output pictures)
         const BufKind ky = planes_kind(b->use_geom), kr = rgb_kind(b->use_geom);
         const size_t yb = w_.yuv ? need(*b, ky) : 0, rb = w_.rgb ? need(*b, kr) : 0, sb = need(*b, kStats);
-        const uint8_t *d_y = b->buf->m[ky].p, *d_r = b->buf->m[kr].p, *d_s = b->buf->m[kStats].p;
+        const size_t hb = need(*b, kHist);
+        const uint8_t *d_y = b->buf->m[ky].p, *d_r = b->buf->m[kr].p, *d_s = b->buf->m[kStats].p, *d_h = b->buf->m[kHist].p;
         const int C = std::min(chunk_pictures(b->params), b->capacity);
         std::string fail;
         for (int g = 0; g < b->total && fail.empty(); g += C) {
@@ -1120,7 +1139,9 @@ void Engine::downloader(int k)
             // MVHP_OUTPUT_SCORE: the chunk's records travel with it, one more piece of the chunk's own download call
             const mvhp_luma_stats_t *recs = nullptr;
             const size_t score_bytes = (size_t)n * sb;
-            if (!grow(oc->stats, (size_t)C * sb)) {
+            // MVHP_OUTPUT_HIST: likewise, one more piece
+            const size_t hist_bytes = (size_t)n * hb;
+            if (!grow(oc->stats, (size_t)C * sb) || !grow(oc->hist, (size_t)C * hb)) {
                 std::lock_guard<std::mutex> l(mu_);
                 put_out(oc);
                 fail = "out of page-locked host memory";
@@ -1129,6 +1150,7 @@ void Engine::downloader(int k)
             const mvhp_luma_bars_t *boxes = nullptr;   // MVHP_OUTPUT_BARS: the same piece, the other record
             if (sb && w_.score) recs = (const mvhp_luma_stats_t *)oc->stats.p;
             if (sb && w_.bars) boxes = (const mvhp_luma_bars_t *)oc->stats.p;
+            const mvhp_plane_hist_t *hists = hb ? (const mvhp_plane_hist_t *)oc->hist.p : nullptr;
             if (w_.jpeg || w_.png) {   // the table rows of the chunk's pictures, then exactly the bytes they name, one piece per file
                 const mvhp_jpeg_entry_t *tab = nullptr;
                 const size_t tb = need(*b, kJpegTab);
@@ -1136,10 +1158,13 @@ void Engine::downloader(int k)
                 bool ok = grow(oc->tab, (size_t)C * tb);
                 if (!ok) err = "out of page-locked host memory";
                 if (ok) {
-                    void *dst[2] = {oc->tab.p, oc->stats.p};
-                    const void *src[2] = {b->buf->m[kJpegTab].p + (size_t)g * tb, sb ? d_s + (size_t)g * sb : nullptr};
-                    size_t nb[2] = {moved, score_bytes};
-                    ok = api_.d2h(cx.dev, sb ? 2 : 1, dst, src, nb, &ms, err) == MVHP_SUCCESS;
+                    void *dst[3] = {oc->tab.p};
+                    const void *src[3] = {b->buf->m[kJpegTab].p + (size_t)g * tb};
+                    size_t nb[3] = {moved};
+                    int np = 1;
+                    if (sb) { dst[np] = oc->stats.p; src[np] = d_s + (size_t)g * sb; nb[np++] = score_bytes; }
+                    if (hb) { dst[np] = oc->hist.p; src[np] = d_h + (size_t)g * hb; nb[np++] = hist_bytes; }
+                    ok = api_.d2h(cx.dev, np, dst, src, nb, &ms, err) == MVHP_SUCCESS;
                     tab = (const mvhp_jpeg_entry_t *)oc->tab.p;
                 }
                 const size_t blob_cap = (size_t)b->total * need(*b, kJpegBlob);
@@ -1172,7 +1197,7 @@ void Engine::downloader(int k)
                     std::lock_guard<std::mutex> l(mu_);
                     if (ok) {
                         st_.d2h_s += (ms + ms2) * 1e-3;
-                        st_.d2h_bytes += moved + score_bytes;
+                        st_.d2h_bytes += moved + score_bytes + hist_bytes;
                         oc->refs = 0;
                         for (int i = 0; i < n; i++) {
                             PicResult &r = results_[(size_t)b->seqs[(size_t)(g + i)]];
@@ -1188,6 +1213,7 @@ void Engine::downloader(int k)
                                 r.err = w_.png ? "the PNG file does not fit into the blob" : "the JPEG file does not fit into the room of the raw picture";
                             }
                             if (recs) r.geom.reserved[1] = mvblank::luma_score(recs[i].sum, recs[i].sumsq, recs[i].samples);
+                            if (hists && r.rc == MVHP_SUCCESS) r.hist = hists + i;
                             r.yuv = nullptr;
                             r.ready = true;
                         }
@@ -1203,20 +1229,21 @@ void Engine::downloader(int k)
             bool ok = grow(oc->yuv, (size_t)C * yb) && grow(oc->rgb, (size_t)C * rb);
             if (!ok) err = "out of page-locked host memory";
             if (ok) {
-                void *dst[3];
-                const void *src[3];
-                size_t nb[3];
+                void *dst[4];
+                const void *src[4];
+                size_t nb[4];
                 int np = 0;
                 if (yb) { dst[np] = oc->yuv.p; src[np] = d_y + (size_t)g * yb; nb[np++] = (size_t)n * yb; }
                 if (rb) { dst[np] = oc->rgb.p; src[np] = d_r + (size_t)g * rb; nb[np++] = (size_t)n * rb; }
                 if (sb) { dst[np] = oc->stats.p; src[np] = d_s + (size_t)g * sb; nb[np++] = score_bytes; }
+                if (hb) { dst[np] = oc->hist.p; src[np] = d_h + (size_t)g * hb; nb[np++] = hist_bytes; }
                 ok = api_.d2h(cx.dev, np, dst, src, nb, &ms, err) == MVHP_SUCCESS;
             }
             {
                 std::lock_guard<std::mutex> l(mu_);
                 if (ok) {
                     st_.d2h_s += (ms + ms2) * 1e-3;
-                    st_.d2h_bytes += (uint64_t)n * (yb + rb) + score_bytes;
+                    st_.d2h_bytes += (uint64_t)n * (yb + rb) + score_bytes + hist_bytes;
                     oc->refs = 0;
                     for (int i = 0; i < n; i++) {
                         PicResult &r = results_[(size_t)b->seqs[(size_t)(g + i)]];
@@ -1230,6 +1257,7 @@ void Engine::downloader(int k)
                             r.geom.reserved[0] = boxes[i].x | boxes[i].y << 16;
                             r.geom.reserved[1] = boxes[i].w | boxes[i].h << 16;
                         }
+                        if (hists) r.hist = hists + i;
                         r.ready = true;
                         oc->refs++;
                     }
@@ -1261,7 +1289,7 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
                    mvhp_picture_sink_t sink, mvhp_picture_sink_ex_t sink_ex, void *user, mvhp_decode_stats_t *stats,
                    std::string &err)
 {
-    if (req && ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_SCORE | MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK | MVHP_OUTPUT_ASPECT | MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE_MASK | MVHP_OUTPUT_BARS | MVHP_OUTPUT_TRIM)) ||
+    if (req && ((req->flags & ~(MVHP_OUTPUT_CROP | MVHP_OUTPUT_BOX | MVHP_OUTPUT_SCORE | MVHP_OUTPUT_ORIENT | MVHP_OUTPUT_ROTATE_MASK | MVHP_OUTPUT_ASPECT | MVHP_OUTPUT_COLOR | MVHP_OUTPUT_COLOR_MODE_MASK | MVHP_OUTPUT_BARS | MVHP_OUTPUT_TRIM | MVHP_OUTPUT_HIST)) ||
                 ((req->flags & MVHP_OUTPUT_COLOR_MODE_MASK) >> MVHP_OUTPUT_COLOR_MODE_SHIFT) > 4 || ((req->flags & MVHP_OUTPUT_BOX) && (req->box_w < 2 || req->box_h < 2)))) {
         err = "malformed output request (box sides must be at least 2, colour modes are 0 to 4)";
         return MVHP_FAILURE;
@@ -1279,7 +1307,8 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         const char *why = sink ?"MVHP_OUTPUT_BARS needs mvhp_engine_decode_ex: its sink gets the box with the geometry"
                           : (out_mask & MVHP_OUT_JPEG) ? "MVHP_OUTPUT_BARS and MVHP_OUT_JPEG both use g->reserved[0]: a call delivers one"
                           : (out_mask & MVHP_OUT_PNG) ? "MVHP_OUTPUT_BARS and MVHP_OUT_PNG both use g->reserved[0]: a call delivers one"
-                          : (req->flags & MVHP_OUTPUT_SCORE) ? "MVHP_OUTPUT_BARS and MVHP_OUTPUT_SCORE both use g->reserved[1]: a call delivers one" : nullptr;
+                          : (req->flags & MVHP_OUTPUT_SCORE) ? "MVHP_OUTPUT_BARS and MVHP_OUTPUT_SCORE both use g->reserved[1]: a call delivers one"
+                          : (req->flags & MVHP_OUTPUT_HIST) ? "MVHP_OUTPUT_BARS and MVHP_OUTPUT_HIST are two probes: a call runs one" : nullptr;
         if (why) { err = why; return MVHP_FAILURE; }
         const uint32_t level = req->reserved >> 24;
         if (level == 255) { err = "MVHP_OUTPUT_BARS: level 255 (1 ... 254; 0 = 24)"; return MVHP_FAILURE; }
@@ -1306,7 +1335,8 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         w_.score = (req_.flags & MVHP_OUTPUT_SCORE) != 0;
         w_.bars = (req_.flags & MVHP_OUTPUT_BARS) != 0;
         w_.bars_level = (req_.reserved >> 24) ? (int)(req_.reserved >> 24) : MVHP_BARS_LEVEL_DEFAULT;
-        req_.flags &= ~(MVHP_OUTPUT_SCORE | MVHP_OUTPUT_BARS);   // (what is left decides the geometry: none = the path of a call without a request)
+        w_.hist = (req_.flags & MVHP_OUTPUT_HIST) != 0;
+        req_.flags &= ~(MVHP_OUTPUT_SCORE | MVHP_OUTPUT_BARS | MVHP_OUTPUT_HIST);   // (what is left decides the geometry: none = the path of a call without a request)
         // colour: only where the call delivers RGB or PNG; otherwise, and always for the geometry, the request without the bits
         w_.color = (req_.flags & MVHP_OUTPUT_COLOR) != 0 && (w_.rgb || w_.png);
         color_mode_ = (int)((req_.flags & MVHP_OUTPUT_COLOR_MODE_MASK) >> MVHP_OUTPUT_COLOR_MODE_SHIFT);
@@ -1469,6 +1499,7 @@ Engine *engine_create(const DeviceApi &api, const mvhp_engine_opts_t *opts, std:
 
 void engine_destroy(Engine *e) { delete e; }
 void engine_release_picture(Engine *e, int seq) { e->release_picture(seq); }
+const mvhp_plane_hist_t *engine_picture_hist(Engine *e, int seq) { return e ? e->picture_hist(seq) : nullptr; }
 
 int engine_decode(Engine *e, const mvhp_stream &s, const int *order, int n_order, int wanted, int out_mask,
                   const mvhp_output_request_t *req, mvhp_picture_sink_t sink, mvhp_picture_sink_ex_t sink_ex, void *user,
@@ -1512,6 +1543,11 @@ MVHP_EXPORT void mvhp_engine_destroy(mvhp_engine_t *h)
 MVHP_EXPORT void mvhp_engine_release_picture(mvhp_engine_t *h, int seq)
 {
     if (h) mvengine::engine_release_picture(h->e, seq);
+}
+
+MVHP_EXPORT const mvhp_plane_hist_t *mvhp_engine_picture_hist(mvhp_engine_t *h, int seq)
+{
+    return h ? mvengine::engine_picture_hist(h->e, seq) : nullptr;
 }
 
 MVHP_EXPORT int mvhp_engine_decode(mvhp_engine_t *h, const mvhp_stream_t *s, const int *order, int n_order, int wanted,

@@ -52,6 +52,8 @@ struct BatchJob {
                                 // picture without one) on the n coded planes in d_yuv -> n records
     mvhp_luma_bars_t *bars;     // NULL: no black-bar probe.  Else mvhp_luma_bars_dev at `bars_level` over the same rectangle of the
     int bars_level;             // same planes -> n records (never beside `stats`, `jpeg` or `png`)
+    mvhp_plane_hist_t *hist;    // NULL: no plane histograms.  Else mvhp_plane_hist_dev over the same rectangle of the same planes ->
+                                // n records of 3104 bytes, 16-byte aligned (beside anything but `bars`)
 };
 struct BatchDone {
     float ms;            // device-side duration of the whole job, one bracketed interval
@@ -59,7 +61,7 @@ struct BatchDone {
 };
 
 // what run_batch can do beyond pictures of the coded size; a job that needs a missing bit fails in the engine, with a message
-enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4, CAP_ORIENT = 8, CAP_PNG = 16, CAP_COLOR = 32, CAP_BARS = 64 };
+enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4, CAP_ORIENT = 8, CAP_PNG = 16, CAP_COLOR = 32, CAP_BARS = 64, CAP_HIST = 128 };
 
 // Every operation blocks its calling thread until the device has finished it; the engine runs one thread per queue
 // and context, which is what overlaps upload(k+1), kernel(k) and download(k-1).  *ms = device-side duration.
@@ -89,6 +91,7 @@ class Engine;
 Engine *engine_create(const DeviceApi &api, const mvhp_engine_opts_t *opts, std::string &err);
 void    engine_destroy(Engine *e);
 void    engine_release_picture(Engine *e, int seq);
+const mvhp_plane_hist_t *engine_picture_hist(Engine *e, int seq);   // mvhp_engine_picture_hist (include/minivideo_hotpath.h)
 int     effective_cores();   // hardware threads cut down to the container's CPU quota
 // one of sink / sink_ex (or neither); req NULL or flags 0: pictures of the coded size, the path without a geometry pass
 int     engine_decode(Engine *e, const mvhp_stream &s, const int *order, int n_order, int wanted, int out_mask,

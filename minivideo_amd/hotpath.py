@@ -63,6 +63,7 @@ MATRIX_BT601, MATRIX_BT709 = 0, 1                                       # mvhp_c
 CHROMA_NEAREST, CHROMA_LEFT, CHROMA_CENTER = 0, 1, 2                    # mvhp_color_params_t::siting (MVHP_CHROMA_*)
 COLOR_MODES = ("auto", "bt601", "bt709", "bt601-full", "bt709-full")    # MVHP_OUTPUT_COLOR_MODE(index); MINIVIDEO_COLOR's values
 OUTPUT_BARS, OUTPUT_TRIM, BARS_LEVEL_SHIFT = 0x1000, 0x2000, 24           # ... probe the black bars (level in reserved bits 24-31); trim them
+OUTPUT_HIST = 0x4000                                                    # ... count the plane histograms (Engine.picture_hist())
 BARS_LEVEL_DEFAULT = 24                                                 # MVHP_BARS_LEVEL_DEFAULT
 ORIENT_SRC_CODED = 1                                                    # mvhp_orient_dev src_flags (MVHP_ORIENT_SRC_CODED)
 
@@ -207,6 +208,47 @@ def blank_choose(scores, min_score):
     """mvhp_blank_choose: index of the first score >= min_score, else of the largest (the earliest on a tie); -1 for none"""
     arr = (C.c_uint32 * max(len(scores), 1))(*[int(x) for x in scores])
     return int(lib().mvhp_blank_choose(arr, len(scores), int(min_score)))
+
+
+class PlaneHist(C.Structure):
+    """mvhp_plane_hist_t: the histograms of the three planes over a picture's rectangle"""
+    _fields_ = [("y", C.c_uint32 * 256), ("cb", C.c_uint32 * 256), ("cr", C.c_uint32 * 256), ("samples", C.c_uint32),
+                ("chroma_samples", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
+PLANE_HIST_DTYPE = np.dtype([("y", "<u4", (256,)), ("cb", "<u4", (256,)), ("cr", "<u4", (256,)), ("samples", "<u4"),
+                             ("chroma_samples", "<u4"), ("reserved", "<u4", (6,))])
+
+
+def _hist_array(hists):
+    """PLANE_HIST_DTYPE records (an array, one record, or raw bytes) -> a contiguous 1-D array of them"""
+    if isinstance(hists, (bytes, bytearray, memoryview)):
+        hists = np.frombuffer(hists, PLANE_HIST_DTYPE)
+    a = np.ascontiguousarray(hists, dtype=PLANE_HIST_DTYPE).reshape(-1)
+    return a
+
+
+def hist_stats(hist):
+    """mvhp_hist_stats: the LumaStats record of the rectangle a PLANE_HIST_DTYPE record was counted over (no device needed)"""
+    a = _hist_array(hist)
+    if a.size != 1:
+        raise ValueError("hist_stats takes one record")
+    out = LumaStats()
+    if lib().mvhp_hist_stats(a.ctypes.data, C.byref(out)) != SUCCESS:
+        raise MiniVideoError("mvhp_hist_stats failed")
+    return out
+
+
+def represent_choose(hists, eligible=None):
+    """mvhp_represent_choose: the index of the candidate closest to the candidates' mean histogram (the earliest on a tie), -1
+    for none; eligible: one flag per record, None = all (no device needed)"""
+    a = _hist_array(hists)
+    el = None
+    if eligible is not None:
+        if len(eligible) != a.size:
+            raise ValueError("one eligibility flag per record")
+        el = (C.c_uint8 * max(a.size, 1))(*[1 if x else 0 for x in eligible])
+    return int(lib().mvhp_represent_choose(a.ctypes.data if a.size else None, int(a.size), el))
 
 
 class LumaBars(C.Structure):
@@ -465,6 +507,14 @@ def lib():
     L.mvhp_luma_stats_dev.argtypes = [vp, pp, pg, vp, i32, vp, vp]
     L.mvhp_set_stats_band.restype = i32
     L.mvhp_set_stats_band.argtypes = [vp, i32]
+    L.mvhp_hist_stats.restype = i32
+    L.mvhp_hist_stats.argtypes = [vp, C.POINTER(LumaStats)]
+    L.mvhp_represent_choose.restype = i32
+    L.mvhp_represent_choose.argtypes = [vp, i32, vp]
+    L.mvhp_plane_hist_dev.restype = i32
+    L.mvhp_plane_hist_dev.argtypes = [vp, pp, pg, vp, i32, vp, vp]
+    L.mvhp_set_hist_band.restype = i32
+    L.mvhp_set_hist_band.argtypes = [vp, i32]
     pb = C.POINTER(LumaBars)
     L.mvhp_bars_need.restype = u32
     L.mvhp_bars_need.argtypes = [u32]
@@ -621,6 +671,18 @@ class HotPath:
         rc = self._L.mvhp_luma_stats_dev(self._h, C.byref(params), C.byref(geom), d_yuv_coded, int(n), d_stats, stream)
         if rc != SUCCESS:
             raise _err(self._L, "mvhp_luma_stats_dev")
+
+    def plane_hist_dev(self, params, geom, d_yuv_coded, n, d_hist, stream=None):
+        """n coded pictures (device) -> n PlaneHist records (PLANE_HIST_DTYPE, device, 16-byte aligned): the luma histogram over
+        geom's crop rectangle, Cb and Cr over the same rectangle halved.  Asynchronous."""
+        rc = self._L.mvhp_plane_hist_dev(self._h, C.byref(params), C.byref(geom), d_yuv_coded, int(n), d_hist, stream)
+        if rc != SUCCESS:
+            raise _err(self._L, "mvhp_plane_hist_dev")
+
+    def set_hist_band(self, rows):
+        """test-only: luma rows per workgroup of plane_hist_dev, 0 = choose (speed only: the records do not depend on it)"""
+        if self._L.mvhp_set_hist_band(self._h, int(rows)) != SUCCESS:
+            raise MiniVideoError("mvhp_set_hist_band(%d) failed" % rows)
 
     def luma_bars_dev(self, params, geom, d_yuv_coded, n, level, d_bars, stream=None):
         """n coded pictures (device) -> n LumaBars records (LUMA_BARS_DTYPE, device) over geom's crop rectangle: a sample is bright
@@ -784,6 +846,8 @@ class Engine:
                                             C.POINTER(OutputRequest), SINK_EX_T, C.c_void_p, C.POINTER(DecodeStats)]
         L.mvhp_engine_release_picture.restype = None
         L.mvhp_engine_release_picture.argtypes = [C.c_void_p, C.c_int]
+        L.mvhp_engine_picture_hist.restype = C.c_void_p
+        L.mvhp_engine_picture_hist.argtypes = [C.c_void_p, C.c_int]
         o = EngineOpts(contexts, host_threads, batch_pictures, chunk_pictures, fail_context, first_device)
         o.reserved[0] = 1 if placed else 0   # bit 0: batch buffers from mvhp_placed_alloc_sets (same as MINIVIDEO_PLACED=1)
         h = C.c_void_p()
@@ -806,8 +870,17 @@ class Engine:
         """gives back a picture whose sink call answered 2 (any thread; the decode call returns when the last one is back)"""
         self._L.mvhp_engine_release_picture(self._h, int(seq))
 
+    def picture_hist(self, seq):
+        """mvhp_engine_picture_hist: the PLANE_HIST_DTYPE record (a copy, shape ()) of picture `seq` of a decode(hist=True) call,
+        for use inside the sink call for `seq` (or for a kept picture until its release); None for a failed picture, without
+        hist=True and at any other time"""
+        p = self._L.mvhp_engine_picture_hist(self._h, int(seq))
+        if not p:
+            return None
+        return np.frombuffer(C.string_at(p, PLANE_HIST_DTYPE.itemsize), PLANE_HIST_DTYPE)[0].copy()
+
     def decode(self, stream_handle, order, wanted=None, want_rgb=False, sink=None, output=None, jpeg=None, restart_mcus=0,
-               score=False, rotate=None, png=False, aspect=False, color=None, bars=None, trim=False):
+               score=False, rotate=None, png=False, aspect=False, color=None, bars=None, trim=False, hist=False):
         """sink(seq, idr, rc, err, params, yuv ndarray | None, rgb ndarray | None) -> 1 accept / 0 reject / -1 stop /
         2 accept and keep until release_picture(seq); the arrays are views of page-locked memory valid only during the call
         (or until the release).  Returns (rc, stats dict).
@@ -830,7 +903,9 @@ class Engine:
         content box in geometry.bars; the pictures are the same bytes.  Not together with jpeg, png or score, and it needs a
         sink (ValueError).
         trim=True: MVHP_OUTPUT_TRIM -- the crop of every picture is trimmed to the box the stream carries (stream_set_trim())
-        where the trim rule accepts it; implies the crop."""
+        where the trim rule accepts it; implies the crop.
+        hist=True: MVHP_OUTPUT_HIST -- the sink is called as for `output` and reads its picture's plane histograms with
+        picture_hist(seq); the pictures are the same bytes.  Not together with bars."""
         order = (C.c_int * len(order))(*order)
         st = DecodeStats()
         n_wanted = len(order) if wanted is None else wanted
@@ -845,10 +920,14 @@ class Engine:
                 raise ValueError("bars travels in the geometry words that carry the file length and the score: not together with jpeg, png or score")
             if sink is None:
                 raise ValueError("bars needs a sink: the boxes are delivered with the geometry")
-        if output is not None or jpeg is not None or score or rotate is not None or png or aspect or color is not None or probe or trim:
+            if hist:
+                raise ValueError("bars and hist are two probes: a call runs one")
+        if output is not None or jpeg is not None or score or rotate is not None or png or aspect or color is not None or probe or trim or hist:
             req = output_request(output, rotate, aspect, color, trim=bool(trim)) or OutputRequest(0, 0, 0, 0)
             if score:
                 req.flags |= OUTPUT_SCORE
+            if hist:
+                req.flags |= OUTPUT_HIST
             if probe:
                 req.flags |= OUTPUT_BARS
                 req.reserved = level << BARS_LEVEL_SHIFT

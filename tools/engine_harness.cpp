@@ -4,7 +4,7 @@
 // lets the sink check that the right picture arrives in the right place, in order, through chunks, batches, several
 // contexts and a re-queue.  Nothing here is part of libminivideo.so.
 //
-// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes> [jpeg | png | score | orient | color <stream whose SPS VUI changes>]]]
+// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes> [jpeg | png | score | bars | hist | orient | color <stream whose SPS VUI changes>]]]
 // The fourth argument adds the geometry mode: mvhp_engine_decode_ex and minivideo_decode under MINIVIDEO_CROP /
 // MINIVIDEO_THUMBNAIL against the stub's resample targets.  A fifth argument adds the JPEG mode (MVHP_OUT_JPEG), the PNG mode (MVHP_OUT_PNG against the stub's PNG operation) or the
 // score mode (MVHP_OUTPUT_SCORE against the stub's picture scores, which sum the stub's coded planes on the CPU), or the orient
@@ -29,6 +29,7 @@
 #include "blank_policy.h"
 #include "decode_engine.h"
 #include "png_format.h"
+#include "represent_policy.h"
 #include "minivideo.h"
 #include "stream_internal.h"
 
@@ -144,6 +145,20 @@ mvhp_luma_bars_t expected_bars(uint64_t h, const mvhp_output_geometry_t *g)
     return b;
 }
 
+// The histograms the stub's plane-histogram operation counts (hist mode): honest counts over the rectangle of the coded planes the
+// batch buffer holds -- the luma as coded_luma() says, both chroma planes one value (0x11 under the pattern, else 0x5a).
+mvhp_plane_hist_t expected_hist(uint64_t h, bool pattern, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g)
+{
+    mvhp_plane_hist_t r{};
+    const size_t Wp = (size_t)p->width_mbs * 16;
+    for (uint32_t y = g->crop_y; y < g->crop_y + g->crop_h; y++)
+        for (uint32_t x = g->crop_x; x < g->crop_x + g->crop_w; x++) r.y[coded_luma(h, pattern, (size_t)y * Wp + x)]++;
+    r.samples = g->crop_w * g->crop_h;
+    r.chroma_samples = (g->crop_w / 2) * (g->crop_h / 2);
+    r.cb[pattern ? 0x11 : 0x5a] = r.cr[pattern ? 0x11 : 0x5a] = r.chroma_samples;
+    return r;
+}
+
 // The one batch operation.  Every job expands its pictures and leaves coded planes; then, as the descriptor asks:
 // * nothing more (pictures of the coded size): the planes are the output, 0x5a with the checksum of the records in bytes 0-7; RGB
 //   0xa5 with the checksum in bytes 8-15;
@@ -162,13 +177,15 @@ mvhp_luma_bars_t expected_bars(uint64_t h, const mvhp_output_geometry_t *g)
 // * scores: honest sums over the rectangle of the coded planes the batch buffer holds.
 // * black bars (bars mode): never beside scores, JPEG or PNG; the level must be 1 .. 254 and is remembered; every picture gets
 //   expected_bars() of its records over the rectangle of the geometry (the coded picture without one).
+// * plane histograms (hist mode): never beside black bars; honest counts over the rectangle of the three coded planes the batch
+//   buffer holds, into records that must be 16-byte aligned.
 // * PNG: the RGB the encoder reads is stamped as above (the fused RGB of a batch of the coded size, the resample or turn target
 //   otherwise; no output planes), and every picture gets a "file" of 64 + checksum % (the longest file - 64) bytes of 0x3d that
 //   starts with bytes 8-15 of that RGB (the checksum) and ends in 0x7a; the blob must be n x the longest file rounded to 16, so
 //   no picture is too big.
 constexpr uint8_t kLastYuv = 0x77, kLastRgb = 0x78, kLastJpeg = 0x79, kLastPng = 0x7a, kLastColor = 0x7b;
 std::atomic<int> g_jpeg_calls{0}, g_stats_calls{0}, g_orient_calls{0}, g_mid_calls{0}, g_png_calls{0}, g_color_calls{0};
-std::atomic<int> g_bars_calls{0}, g_bars_level{0};
+std::atomic<int> g_bars_calls{0}, g_bars_level{0}, g_hist_calls{0};
 std::atomic<uint32_t> g_watch_crop[4];   // bars mode: launches whose geometry has this crop rectangle are counted
 std::atomic<int> g_watch_hits{0};
 uint8_t color_tag(const mvhp_color_params_t &c) { return (uint8_t)(0xc0 | (c.matrix << 3) | (c.full_range << 2) | c.siting); }
@@ -225,6 +242,11 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
     if (j.bars && (j.stats || j.jpeg || j.png || j.bars_level < 1 || j.bars_level > 254 || n <= 0 || rect.crop_w == 0 || rect.crop_h == 0 ||
                    rect.crop_x + rect.crop_w > p->width_mbs * 16 || rect.crop_y + rect.crop_h > p->height_mbs * 16)) {
         err = "stub: black-bar launch without buffers, level or rectangle";
+        return MVHP_FAILURE;
+    }
+    if (j.hist && (j.bars || ((uintptr_t)j.hist & 15) || n <= 0 || rect.crop_w < 2 || rect.crop_h < 2 || ((rect.crop_x | rect.crop_y | rect.crop_w | rect.crop_h) & 1) ||
+                   rect.crop_x + rect.crop_w > p->width_mbs * 16 || rect.crop_y + rect.crop_h > p->height_mbs * 16)) {
+        err = "stub: plane-histogram launch without buffers or rectangle";
         return MVHP_FAILURE;
     }
     if (g && g->crop_x == g_watch_crop[0] && g->crop_y == g_watch_crop[1] && g->crop_w == g_watch_crop[2] && g->crop_h == g_watch_crop[3]) g_watch_hits++;
@@ -294,6 +316,21 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
             j.stats[i] = st;
         }
         if (j.bars) j.bars[i] = expected_bars(h, &rect);
+        if (j.hist) {
+            mvhp_plane_hist_t r{};
+            const size_t Wp = (size_t)p->width_mbs * 16, Hp = (size_t)p->height_mbs * 16;
+            const uint8_t *cb = coded + Wp * Hp, *cr = cb + Wp * Hp / 4;
+            for (uint32_t y = rect.crop_y; y < rect.crop_y + rect.crop_h; y++)
+                for (uint32_t x = rect.crop_x; x < rect.crop_x + rect.crop_w; x++) r.y[coded[(size_t)y * Wp + x]]++;
+            for (uint32_t y = rect.crop_y / 2; y < (rect.crop_y + rect.crop_h) / 2; y++)
+                for (uint32_t x = rect.crop_x / 2; x < (rect.crop_x + rect.crop_w) / 2; x++) {
+                    r.cb[cb[(size_t)y * (Wp / 2) + x]]++;
+                    r.cr[cr[(size_t)y * (Wp / 2) + x]]++;
+                }
+            r.samples = rect.crop_w * rect.crop_h;
+            r.chroma_samples = (rect.crop_w / 2) * (rect.crop_h / 2);
+            j.hist[i] = r;
+        }
     }
     std::this_thread::sleep_for(std::chrono::microseconds(200));
     done.ms = j.stats ? 0.25f : 0.2f;
@@ -301,12 +338,13 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
     done.waves = 8;
     if (j.stats) g_stats_calls++;
     if (j.bars) { g_bars_calls++; g_bars_level = j.bars_level; }
+    if (j.hist) g_hist_calls++;
     return MVHP_SUCCESS;
 }
 
 mvengine::DeviceApi g_stub = {stub_device_count, stub_host_alloc, stub_host_free, stub_ctx_create, stub_ctx_destroy,
                                     stub_dev_alloc, stub_dev_free, stub_dev_free_bytes, stub_copy_n, stub_copy_n, stub_run_batch,
-                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_PNG | mvengine::CAP_COLOR | mvengine::CAP_BARS,
+                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_PNG | mvengine::CAP_COLOR | mvengine::CAP_BARS | mvengine::CAP_HIST,
                                     nullptr, nullptr};   // (no placed arena on the stub device)
 
 uint64_t picture_checksum(const mvhp_stream &s, int idr)
@@ -607,6 +645,64 @@ struct CheckS {
         }
         c.ok++;
         return 1;
+    }
+};
+
+// sink of the hist mode: everything CheckS checks (with `scored`: the score too; without it reserved[1] is 0), and
+// mvhp_engine_picture_hist: inside the sink call the picture's own record, the stub's counts over the geometry's rectangle; NULL for
+// a failed picture, for a picture that is not in its sink call, and without the flag.  Every fourth picture is kept (verdict 2): its
+// record stays readable until the next picture's sink call gives it back, and is NULL from then on.
+struct CheckH {
+    CheckS base;
+    mvhp_engine_t *e = nullptr;
+    bool flag = true, scored = false;
+    int bad = 0, records = 0, kept = -1, kept_checked = 0, n_order = 0;
+    mvhp_plane_hist_t kept_want{};
+    static int sink(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
+                    const uint8_t *yuv, const uint8_t *rgb)
+    {
+        CheckH &c = *static_cast<CheckH *>(user);
+        if (c.kept >= 0) {   // the picture kept in the previous call: still there, then given back, then gone
+            const mvhp_plane_hist_t *k = mvhp_engine_picture_hist(c.e, c.kept);
+            if (!k || memcmp(k, &c.kept_want, sizeof(*k)) != 0) c.bad++;
+            mvhp_engine_release_picture(c.e, c.kept);
+            if (mvhp_engine_picture_hist(c.e, c.kept) != nullptr) c.bad++;
+            c.kept = -1;
+            c.kept_checked++;
+        }
+        const mvhp_plane_hist_t *got = mvhp_engine_picture_hist(c.e, seq);
+        if (mvhp_engine_picture_hist(c.e, seq + 1) || mvhp_engine_picture_hist(c.e, seq - 1) || mvhp_engine_picture_hist(c.e, -1) ||
+            mvhp_engine_picture_hist(c.e, c.n_order)) c.bad++;
+        mvhp_output_geometry_t g2{};
+        if (g) g2 = *g;
+        if (!c.scored && g2.reserved[1] != 0) c.bad++;
+        const int ok0 = c.base.ok;
+        if (!c.scored && rc == MVHP_SUCCESS) {   // (CheckS expects the score in reserved[1]: hand it the one it would compute)
+            mvhp_output_geometry_t want;
+            if (mvhp_output_geometry(c.base.s, idr, &c.base.req, &want) == MVHP_SUCCESS) {
+                const bool coded = want.crop_x == 0 && want.crop_y == 0 && want.out_w == p->width_mbs * 16 && want.out_h == p->height_mbs * 16 &&
+                                   want.crop_w == want.out_w && want.crop_h == want.out_h;
+                const mvhp_luma_stats_t st = expected_stats(picture_checksum(*c.base.s, idr), (c.base.mask & MVHP_OUT_JPEG) || !coded, p, &want);
+                g2.reserved[1] = mvblank::luma_score(st.sum, st.sumsq, st.samples);
+            }
+        }
+        const int verdict = CheckS::sink(&c.base, seq, idr, rc, err, p, g ? &g2 : nullptr, yuv, rgb);
+        if (rc != MVHP_SUCCESS || c.base.ok == ok0 || !c.flag) {
+            if (got) c.bad++;
+            return verdict;
+        }
+        mvhp_output_geometry_t want;
+        if (!got || ((uintptr_t)got & 15) || mvhp_output_geometry(c.base.s, idr, &c.base.req, &want) != MVHP_SUCCESS) { c.bad++; return verdict; }
+        const bool coded = want.crop_x == 0 && want.crop_y == 0 && want.out_w == p->width_mbs * 16 && want.out_h == p->height_mbs * 16 &&
+                           want.crop_w == want.out_w && want.crop_h == want.out_h;
+        const mvhp_plane_hist_t exp = expected_hist(picture_checksum(*c.base.s, idr), (c.base.mask & MVHP_OUT_JPEG) || !coded, p, &want);
+        if (memcmp(got, &exp, sizeof(exp)) != 0) c.bad++;
+        mvhp_luma_stats_t from_hist;   // one probe serves both features: the score of the histogram is the picture's score
+        mvrep::hist_stats(*got, from_hist);
+        if (mvblank::luma_score(from_hist.sum, from_hist.sumsq, from_hist.samples) != g2.reserved[1]) c.bad++;
+        c.records++;
+        if (seq % 4 == 0 && seq + 1 < c.n_order) { c.kept = seq; c.kept_want = exp; return 2; }
+        return verdict;
     }
 };
 
@@ -1872,6 +1968,263 @@ int main(int argc, char **argv)
             }
             unsetenv("MINIVIDEO_SKIP_BLANK");
             printf("SCORE MODE DONE\n");
+        }
+        if (argc > 5 && !strcmp(argv[5], "hist")) {   // ---- hist mode: MVHP_OUTPUT_HIST against the stub's plane-histogram operation ----
+            std::vector<int> order;
+            for (int k = 0; k < 3 * n3; k++) order.push_back(k % n3);
+            auto run_hist = [&](const char *name, mvhp_engine_opts_t o, int mask, mvhp_output_request_t req, uint32_t extra, CheckH &c,
+                                mvhp_decode_stats_t &stats) {
+                mvhp_engine_t *e = nullptr;
+                if (mvhp_engine_create(&o, &e) != MVHP_SUCCESS) { failures++; return MVHP_FAILURE; }
+                c.base.s = &s3; c.base.req = req; c.base.order = order; c.base.mask = mask;
+                c.e = e; c.n_order = (int)order.size();
+                c.flag = (extra & MVHP_OUTPUT_HIST) != 0; c.scored = (extra & MVHP_OUTPUT_SCORE) != 0;
+                req.flags |= extra;
+                const int rc = mvhp_engine_decode_ex(e, &s3, order.data(), (int)order.size(), (int)order.size(), mask, &req, CheckH::sink, &c, &stats);
+                for (int k = -1; k <= (int)order.size(); k++) EXPECT(mvhp_engine_picture_hist(e, k) == nullptr);   // the call is over
+                mvhp_engine_destroy(e);
+                printf("%-28s rc=%d mask=%d flags=%#x ok=%u failed=%u batches=%u geometry=%u requeued=%u d2h=%llu records=%d kept=%d\n", name, rc, mask,
+                       req.flags, stats.pictures_ok, stats.pictures_failed, stats.batches, stats.geometry_launches, stats.batches_requeued,
+                       (unsigned long long)stats.d2h_bytes, c.records, c.kept_checked);
+                return rc;
+            };
+            EXPECT(mvhp_engine_picture_hist(nullptr, 0) == nullptr);
+            for (int contexts = 1; contexts <= 3; contexts++)
+                for (int mask : {0, MVHP_OUT_RGB, MVHP_OUT_RGB_ONLY, MVHP_OUT_JPEG})
+                    for (mvhp_output_request_t req : {mvhp_output_request_t{0, 0, 0, 0}, crop, box}) {
+                        if (mask == MVHP_OUT_JPEG) req.reserved = MVHP_JPEG_REQUEST(80, 0);
+                        mvhp_engine_opts_t o = base; o.contexts = contexts; o.chunk_pictures = 2; o.batch_pictures = contexts == 1 ? 64 : 3;
+                        // without the flag: the same pictures, no record, the operation never called
+                        const int calls0 = g_hist_calls;
+                        CheckH c0; mvhp_decode_stats_t st0;
+                        EXPECT(run_hist("hist: flag off", o, mask, req, 0, c0, st0) == MVHP_SUCCESS);
+                        EXPECT(c0.bad == 0 && c0.base.bad == 0 && c0.records == 0 && g_hist_calls == calls0);
+                        // with it (three contexts: the first batch of context 0 fails and is re-queued, and counted again), alone and
+                        // beside the score
+                        o.fail_context = contexts == 3 ? 0 : -1;
+                        for (uint32_t extra : {(uint32_t)MVHP_OUTPUT_HIST, (uint32_t)(MVHP_OUTPUT_HIST | MVHP_OUTPUT_SCORE)}) {
+                            const int calls1 = g_hist_calls, stats1 = g_stats_calls;
+                            CheckH c; mvhp_decode_stats_t st;
+                            EXPECT(run_hist(req.flags & MVHP_OUTPUT_BOX ? "hist box" : req.flags ? "hist crop" : "hist coded size", o, mask, req, extra, c,
+                                            st) == MVHP_SUCCESS);
+                            EXPECT(c.bad == 0 && c.base.bad == 0 && c.base.no_op == 0 && c.base.calls == (int)order.size());
+                            EXPECT(c.base.ok == (int)st.pictures_ok && c.base.ok == (int)st0.pictures_ok && c.records == c.base.ok && c.kept_checked > 0);
+                            const uint64_t per = 3104ull + ((extra & MVHP_OUTPUT_SCORE) ? 32ull : 0ull);
+                            EXPECT(st.d2h_bytes == st0.d2h_bytes + per * (uint64_t)c.base.formed_n);   // exactly one record per picture of a batch
+                            EXPECT((int)st.batches_requeued == (contexts == 3 ? 1 : 0));
+                            EXPECT(g_hist_calls - calls1 == (int)st.batches);   // one call behind every launch that succeeded
+                            EXPECT(g_stats_calls - stats1 == ((extra & MVHP_OUTPUT_SCORE) ? (int)st.batches : 0));
+                            if (!req.flags) EXPECT(st.geometry_launches == 0);   // the flag alone: still the coded-size path
+                        }
+                    }
+            {   // a device table without the operation: every picture of the call fails with the message, nothing is launched
+                g_stub.caps &= ~mvengine::CAP_HIST;
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 4;
+                mvhp_engine_t *e = nullptr;
+                EXPECT(mvhp_engine_create(&o, &e) == MVHP_SUCCESS);
+                struct NoOp { mvhp_engine_t *e; int calls = 0, no_op = 0, other = 0, records = 0; } n{e};
+                auto sink = [](void *user, int seq, int, int rc, const char *err, const mvhp_stream_params_t *, const mvhp_output_geometry_t *,
+                               const uint8_t *, const uint8_t *) {
+                    NoOp &c = *static_cast<NoOp *>(user);
+                    c.calls++;
+                    if (rc != MVHP_SUCCESS && err && strstr(err, "plane-histogram operation")) c.no_op++;
+                    else if (rc == MVHP_SUCCESS) c.other++;
+                    if (mvhp_engine_picture_hist(c.e, seq)) c.records++;
+                    return 0;
+                };
+                mvhp_output_request_t req = crop;
+                req.flags |= MVHP_OUTPUT_HIST;
+                mvhp_decode_stats_t st;
+                const int calls0 = g_hist_calls, recon0 = g_recon_calls + g_geometry_calls + g_jpeg_calls;
+                int formed = 0;
+                for (int idr : order) { mvhp_output_geometry_t g; formed += mvhp_output_geometry(&s3, idr, &crop, &g) == MVHP_SUCCESS; }
+                const int rc = mvhp_engine_decode_ex(e, &s3, order.data(), (int)order.size(), (int)order.size(), 0, &req, sink, &n, &st);
+                printf("%-28s rc=%d calls=%d no operation=%d\n", "hist: table without it", rc, n.calls, n.no_op);
+                EXPECT(rc == MVHP_FAILURE && n.other == 0 && n.records == 0 && n.no_op == formed && formed > 0 && g_hist_calls == calls0);
+                EXPECT(g_recon_calls + g_geometry_calls + g_jpeg_calls == recon0);
+                mvhp_engine_destroy(e);
+                CheckG cg;   // ... and a call without the flag is not affected
+                EXPECT(run_ex("hist: table without it, off", o, s3, order, 0, crop, cg, st) == MVHP_SUCCESS && cg.bad == 0);
+                g_stub.caps |= mvengine::CAP_HIST;
+            }
+            {   // two probes in one call are refused, with a message and before any work
+                mvhp_engine_opts_t o = base; o.contexts = 1;
+                std::string why;
+                mvengine::Engine *pe = mvengine::engine_create(g_stub, &o, why);
+                EXPECT(pe != nullptr);
+                const int launches0 = g_recon_calls + g_geometry_calls + g_bars_calls + g_hist_calls;
+                mvhp_output_request_t req{MVHP_OUTPUT_HIST | MVHP_OUTPUT_BARS, 0, 0, 0};
+                CheckB c; c.s = &s3; c.order = order; mvhp_decode_stats_t st;
+                const int rc = pe ? mvengine::engine_decode(pe, s3, order.data(), (int)order.size(), (int)order.size(), 0, &req, nullptr, CheckB::sink, &c,
+                                                            &st, why) : MVHP_SUCCESS;
+                printf("%-28s rc=%d message: %s\n", "hist with bars", rc, why.c_str());
+                EXPECT(rc == MVHP_FAILURE && c.calls == 0 && why.find("MVHP_OUTPUT_HIST") != std::string::npos && why.find("MVHP_OUTPUT_BARS") != std::string::npos);
+                EXPECT(pe && mvengine::engine_picture_hist(pe, 0) == nullptr);
+                if (pe) mvengine::engine_destroy(pe);
+                EXPECT(g_recon_calls + g_geometry_calls + g_bars_calls + g_hist_calls == launches0);
+            }
+            {   // minivideo_decode under MINIVIDEO_REPRESENTATIVE=1 on the stub device: three engine calls on one engine.  The stub's
+                // histograms are functions of the records' checksum and the rectangle, so the winners, the order lists of passes 2
+                // and 3 (the second stats line) and the files -- which start with the records' checksum -- are known beforehand.
+                char tmpl[] = "/tmp/mvharness_XXXXXX";
+                const char *dir = mkdtemp(tmpl);
+                char cwd[4096];
+                EXPECT(dir != nullptr && getcwd(cwd, sizeof(cwd)) != nullptr);
+                std::string in = argv[4];
+                if (in[0] != '/') in = std::string(cwd) + "/" + in;
+                EXPECT(dir && chdir(dir) == 0);
+                setenv("MINIVIDEO_REPRESENTATIVE", "1", 1);
+                setenv("MINIVIDEO_STATS", "1", 1);
+                struct Case { const char *name; bool crop; const char *blank_variance; const char *alts; int num; const char *batch, *gpus, *writers; };
+                int moved = 0, resized = 0, blank_ruled = 0;
+                for (const Case &cs : {Case{"plain", false, nullptr, nullptr, 1, nullptr, nullptr, "0"},
+                                       Case{"plain, batches of 1", false, nullptr, nullptr, 1, "1", nullptr, "0"},
+                                       Case{"plain, 3 contexts", false, nullptr, nullptr, 1, nullptr, "3", "2"},
+                                       Case{"3 alternates, 4 files", false, nullptr, "3", 4, nullptr, nullptr, "2"},
+                                       Case{"3 alternates, 4 files, b=1", false, nullptr, "3", 4, "1", "3", "0"},
+                                       Case{"all files: no alternates", false, nullptr, nullptr, n3, nullptr, nullptr, "2"},
+                                       Case{"cropped", true, nullptr, "16", 2, nullptr, nullptr, "0"},
+                                       Case{"cropped, batches of 1", true, nullptr, "16", 2, "1", "3", "0"},
+                                       Case{"cropped, with blank skipping", true, "5000", "16", 2, nullptr, nullptr, "0"},
+                                       Case{"all blank", false, "16256", "5", 2, nullptr, nullptr, "0"}}) {
+                    const int a = cs.alts ? atoi(cs.alts) : 8;
+                    if (cs.alts) setenv("MINIVIDEO_REPRESENTATIVE_ALTERNATES", cs.alts, 1); else unsetenv("MINIVIDEO_REPRESENTATIVE_ALTERNATES");
+                    if (cs.crop) setenv("MINIVIDEO_CROP", "1", 1); else unsetenv("MINIVIDEO_CROP");
+                    if (cs.batch) setenv("MINIVIDEO_BATCH", cs.batch, 1); else unsetenv("MINIVIDEO_BATCH");
+                    if (cs.gpus) setenv("MINIVIDEO_FAKE_GPUS", cs.gpus, 1); else unsetenv("MINIVIDEO_FAKE_GPUS");
+                    setenv("MINIVIDEO_WRITERS", cs.writers, 1);
+                    if (cs.blank_variance) {
+                        setenv("MINIVIDEO_SKIP_BLANK", "1", 1);
+                        setenv("MINIVIDEO_BLANK_VARIANCE", cs.blank_variance, 1);
+                        setenv("MINIVIDEO_BLANK_ALTERNATES", "1", 1);   // (not read: the alternates are the representative switch's)
+                    } else { unsetenv("MINIVIDEO_SKIP_BLANK"); unsetenv("MINIVIDEO_BLANK_VARIANCE"); unsetenv("MINIVIDEO_BLANK_ALTERNATES"); }
+                    const uint32_t min_score = 16u * (uint32_t)(cs.blank_variance ? atoi(cs.blank_variance) : 256);
+                    // what must happen.  Unfiltered: the slots are the first `num` pictures that decode (under the crop IDRs
+                    // whose crop leaves nothing fail and the next one takes the slot)
+                    const mvhp_output_request_t r1{cs.crop ? MVHP_OUTPUT_CROP : 0u, 0, 0, 0};
+                    std::vector<int> slots;
+                    for (int idr = 0; idr < n3 && (int)slots.size() < cs.num; idr++) {
+                        mvhp_output_geometry_t g;
+                        if (mvhp_output_geometry(&s3, idr, &r1, &g) == MVHP_SUCCESS) slots.push_back(idr);
+                    }
+                    auto hist_of = [&](int idr, mvhp_plane_hist_t &h) {
+                        mvhp_output_geometry_t g;
+                        mvhp_stream_params_t p;
+                        if (mvhp_output_geometry(&s3, idr, &r1, &g) != MVHP_SUCCESS || mvhp_stream_params(&s3, idr, &p) != MVHP_SUCCESS) return false;
+                        const bool coded = g.crop_x == 0 && g.crop_y == 0 && g.out_w == p.width_mbs * 16 && g.out_h == p.height_mbs * 16 &&
+                                           g.crop_w == g.out_w && g.crop_h == g.out_h;
+                        h = expected_hist(picture_checksum(s3, idr), !coded, &p, &g);
+                        return true;
+                    };
+                    std::vector<int> finals, want2, want3;
+                    for (int k = 0; k < (int)slots.size(); k++) {
+                        std::vector<mvhp_plane_hist_t> cand(1);
+                        std::vector<int> cand_idr{slots[(size_t)k]};
+                        EXPECT(hist_of(slots[(size_t)k], cand[0]));
+                        for (int i : mvblank::alternates(slots, n3, a, k)) {
+                            want2.push_back(i);
+                            mvhp_plane_hist_t h;
+                            if (hist_of(i, h)) { cand.push_back(h); cand_idr.push_back(i); }
+                        }
+                        std::vector<uint8_t> el;
+                        std::vector<uint32_t> sc;
+                        for (const mvhp_plane_hist_t &h : cand) {
+                            mvhp_luma_stats_t ls;
+                            mvrep::hist_stats(h, ls);
+                            sc.push_back(mvblank::luma_score(ls.sum, ls.sumsq, ls.samples));
+                            el.push_back(sc.back() >= min_score);
+                            if (h.samples != cand[0].samples) resized++;
+                        }
+                        int w = mvrep::choose(cand.data(), (int)cand.size(), cs.blank_variance ? el.data() : nullptr);
+                        if (w < 0) { w = mvblank::choose(sc.data(), (int)sc.size(), min_score); blank_ruled++; }
+                        finals.push_back(cand_idr[(size_t)w]);
+                        if (w > 0) { want3.push_back(cand_idr[(size_t)w]); moved++; }
+                    }
+                    auto list = [](const std::vector<int> &v) {
+                        std::string l;
+                        for (int i : v) l += " " + std::to_string(i);
+                        return v.empty() ? std::string(" none") : l;
+                    };
+                    const std::string want_line = "pass 2 order:" + list(want2) + "; pass 3 order:" + list(want3) + "\n";
+                    MediaFile_t *m = nullptr;
+                    EXPECT(minivideo_open(in.c_str(), &m) == SUCCESS);
+                    EXPECT(m && minivideo_parse(m, false, true, false) == SUCCESS);
+                    const int calls0 = g_hist_calls, stats0 = g_stats_calls;
+                    fflush(stdout);
+                    fflush(stderr);
+                    char errfile[] = "stderr.txt";
+                    const int saved = dup(2);
+                    FILE *ef = fopen(errfile, "w");
+                    EXPECT(ef != nullptr);
+                    if (ef) dup2(fileno(ef), 2);
+                    const int rc = m ? minivideo_decode(m, ".", PICTURE_YUV420, 75, cs.num, PICTURE_UNFILTERED) : FAILURE;
+                    fflush(stderr);
+                    dup2(saved, 2);
+                    close(saved);
+                    if (ef) fclose(ef);
+                    const std::vector<uint8_t> eb = read_file(errfile);
+                    remove(errfile);
+                    const std::string etext(eb.begin(), eb.end());
+                    EXPECT(rc == SUCCESS && g_hist_calls > calls0 && g_stats_calls == stats0);   // (the score comes from the histogram)
+                    EXPECT(etext.find(want_line) != std::string::npos);
+                    EXPECT(etext.find(std::to_string(want2.size()) + " candidates listed") != std::string::npos);
+                    EXPECT(etext.find(std::to_string(want3.size()) + " files replaced") != std::string::npos);
+                    EXPECT(etext.find("blank pictures:") == std::string::npos);   // blank skipping's own pass is not run
+                    int good = 0;
+                    for (int k = 0; k < (int)slots.size(); k++) {
+                        const std::string name = std::string(m->file_name) + (cs.num > 1 ? "_" + std::to_string(k) : "") + ".yuv";
+                        const std::vector<uint8_t> f = read_file(name);
+                        remove(name.c_str());
+                        uint64_t got = 0;
+                        if (f.size() >= 8) memcpy(&got, f.data(), 8);
+                        if (got == picture_checksum(s3, finals[(size_t)k])) good++;
+                        EXPECT(read_file(name + ".part").empty());
+                    }
+                    printf("%-28s %s: n=%d right picture in %d files; expected %s", "public API, representative", cs.name, cs.num, good, want_line.c_str());
+                    EXPECT(good == (int)slots.size() && (int)slots.size() == std::min(cs.num, n3));
+                    EXPECT(minivideo_close(&m) == SUCCESS);
+                }
+                EXPECT(moved >= 3 && resized >= 1 && blank_ruled >= 1);   // (slots did give way; sizes did differ; the blank rule did decide)
+                for (const char *v : {"MINIVIDEO_REPRESENTATIVE", "MINIVIDEO_REPRESENTATIVE_ALTERNATES", "MINIVIDEO_STATS", "MINIVIDEO_CROP", "MINIVIDEO_BATCH",
+                                      "MINIVIDEO_FAKE_GPUS", "MINIVIDEO_WRITERS", "MINIVIDEO_SKIP_BLANK", "MINIVIDEO_BLANK_VARIANCE", "MINIVIDEO_BLANK_ALTERNATES"})
+                    unsetenv(v);
+                EXPECT(chdir(cwd) == 0);
+                rmdir(dir);
+            }
+            // malformed values of the two switches of minivideo_decode: FAILURE, with a message, before the device is touched --
+            // whether or not the feature is on
+            struct Bad { const char *var, *value, *on; };
+            for (const Bad &b : {Bad{"MINIVIDEO_REPRESENTATIVE_ALTERNATES", "abc", "1"}, Bad{"MINIVIDEO_REPRESENTATIVE_ALTERNATES", "0", "1"},
+                                 Bad{"MINIVIDEO_REPRESENTATIVE_ALTERNATES", "17", "0"}, Bad{"MINIVIDEO_REPRESENTATIVE", "yes", nullptr},
+                                 Bad{"MINIVIDEO_REPRESENTATIVE", "2", nullptr}}) {
+                if (b.on) setenv("MINIVIDEO_REPRESENTATIVE", b.on, 1);
+                setenv(b.var, b.value, 1);
+                MediaFile_t *m = nullptr;
+                EXPECT(minivideo_open(argv[4], &m) == SUCCESS);
+                EXPECT(m && minivideo_parse(m, false, true, false) == SUCCESS);
+                const int ctx_before = g_ctx_created, launches_before = g_recon_calls + g_geometry_calls + g_hist_calls;
+                fflush(stdout);
+                fflush(stderr);
+                int pipefd[2];
+                EXPECT(pipe(pipefd) == 0);
+                const int saved = dup(2);
+                dup2(pipefd[1], 2);
+                const int rc = m ? minivideo_decode(m, ".", PICTURE_YUV420, 75, n3, PICTURE_UNFILTERED) : SUCCESS;
+                fflush(stderr);
+                dup2(saved, 2);
+                close(saved);
+                close(pipefd[1]);
+                char msg[512] = "";
+                const ssize_t got = read(pipefd[0], msg, sizeof(msg) - 1);
+                close(pipefd[0]);
+                printf("%-28s %s='%s' rc=%d message: %s", "malformed representative switch", b.var, b.value, rc, got > 0 ? msg : "(none)\n");
+                EXPECT(rc == FAILURE && got > 0 && strstr(msg, b.var) != nullptr);
+                EXPECT(g_ctx_created == ctx_before && g_recon_calls + g_geometry_calls + g_hist_calls == launches_before);
+                EXPECT(minivideo_close(&m) == SUCCESS);
+                unsetenv(b.var);
+                unsetenv("MINIVIDEO_REPRESENTATIVE");
+            }
+            printf("HIST MODE DONE\n");
         }
         if (argc > 5 && !strcmp(argv[5], "bars")) {   // ---- bars mode: MVHP_OUTPUT_BARS / MVHP_OUTPUT_TRIM against the stub's black-bar operation ----
             std::vector<int> order;

@@ -71,17 +71,20 @@ int main(int argc, char *argv[])
         else if (!strcmp(argv[i], "-z")) setenv("MINIVIDEO_PNG", "1", 1);    // PNG files are compressed, and made on the GPU
         else if (!strcmp(argv[i], "-b")) setenv("MINIVIDEO_SKIP_BLANK", "1", 1);   // blank pictures (black, faded, flat) give way to later ones
         else if (!strcmp(argv[i], "-t")) setenv("MINIVIDEO_TRIM", "1", 1);         // black bars (letterbox, pillarbox) are trimmed off every picture
+        else if (!strcmp(argv[i], "-p")) setenv("MINIVIDEO_REPRESENTATIVE", "1", 1);   // each file holds the picture that looks most like its neighbours
         else if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) help = true;
         else fprintf(stderr, "* Unknown argument '%s'\n", argv[i]);
     }
     if (!in || help) {
         printf("* Usage:\nmini_thumbnailer -i <filepath> [-o <directory>] [-f picture_format][-q picture_quality]"
-               "[-n picture_number] [-e extraction_mode] [-c] [-s <width>x<height>] [-r auto|0|90|180|270] [-a] [-m auto|bt601|bt709|bt601-full|bt709-full] [-j] [-z] [-b] [-t]\n"
+               "[-n picture_number] [-e extraction_mode] [-c] [-s <width>x<height>] [-r auto|0|90|180|270] [-a] [-m auto|bt601|bt709|bt601-full|bt709-full] [-j] [-z] [-b] [-t] [-p]\n"
                "-z : PNG files (-f png, and -f jpg without -j) are compressed, and made on the GPU (MINIVIDEO_PNG=1)\n"
                "-b : skip blank pictures (MINIVIDEO_SKIP_BLANK=1; MINIVIDEO_BLANK_VARIANCE=<0..16256, default 256>, "
                "MINIVIDEO_BLANK_ALTERNATES=<1..16, default 4>)\n"
                "-t : trim black bars (MINIVIDEO_TRIM=1; MINIVIDEO_TRIM_LEVEL=<1..254, default 24>, "
-               "MINIVIDEO_TRIM_PROBES=<1..64, default 8>)\n");
+               "MINIVIDEO_TRIM_PROBES=<1..64, default 8>)\n"
+               "-p : representative pictures: each file holds, of its picture and the IDR pictures that follow it, the one nearest "
+               "their mean histogram (MINIVIDEO_REPRESENTATIVE=1; MINIVIDEO_REPRESENTATIVE_ALTERNATES=<1..16, default 8>)\n");
         return EXIT_FAILURE;
     }
     mark("main, arguments read");
