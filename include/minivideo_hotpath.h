@@ -646,6 +646,47 @@ MVHP_EXPORT int      mvhp_represent_choose(const mvhp_plane_hist_t *h, int n, co
 MVHP_EXPORT int      mvhp_plane_hist_dev(mvhp_ctx_t *ctx, const mvhp_stream_params_t *p, const mvhp_output_geometry_t *g,
                                          const uint8_t *d_yuv_coded, int n, mvhp_plane_hist_t *d_hist, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Tensor output (opt-in; DESIGN.md 3 "Tensor output"): dense RGB8 pictures -> a batch tensor of one fixed shape, in the caller's
+ * element type and layout, normalised and padded on the device, so that what a model reads never leaves it.
+ *
+ * Arithmetic, the whole contract: a sample c (0 .. 255) of colour k becomes fmaf((float)c, scale[k], bias[k]) -- one IEEE
+ * binary32 fused multiply-add, one rounding -- stored as it is (F32) or rounded to nearest-even to binary16 (F16) or bfloat16
+ * (BF16).  Subnormal results are kept in all three types; F16 overflows to infinity as IEEE says.
+ * Placement: the picture sits at ox = (canvas_w - src_w) / 2, oy = (canvas_h - src_h) / 2 of the canvas (floor division);
+ * every other element is the value of pad_rgb's sample of its colour under the same arithmetic.  NCHW is three planes of
+ * canvas_h x canvas_w, NHWC interleaved; MVHP_TENSOR_BGR puts the planes / the interleave in the order B, G, R (scale, bias and
+ * pad_rgb stay indexed by colour).  Out of scope: enlarging, a "cover" crop, canvases per picture, picture files.
+ * ------------------------------------------------------------------------- */
+#define MVHP_TENSOR_F32 0
+#define MVHP_TENSOR_F16 1
+#define MVHP_TENSOR_BF16 2
+#define MVHP_TENSOR_NCHW 0
+#define MVHP_TENSOR_NHWC 1
+#define MVHP_TENSOR_BGR  1u          /* flags: channel planes / interleave order B,G,R instead of R,G,B */
+typedef struct mvhp_tensor_params {
+    uint32_t src_w, src_h;           /* dense RGB8 pictures in, as every RGB path of the library leaves them (1..16384) */
+    uint32_t canvas_w, canvas_h;     /* tensor H x W; 0,0 = src size; each >= src side, <= 16384, odd allowed */
+    uint32_t dtype, layout, flags;
+    uint32_t pad_rgb;                /* 0x00RRGGBB: colour of the canvas outside the picture */
+    float    scale[3], bias[3];      /* per R, G, B (indexed by colour, not by output position) */
+} mvhp_tensor_params_t;
+/* Bytes of one picture's tensor (3 x canvas_h x canvas_w elements); 0 = bad parameters (an enum value outside those above, an
+ * unknown flag bit, a side of 0 or above 16384, one canvas side 0 and the other not, a canvas smaller than the picture).  A host
+ * function. */
+MVHP_EXPORT size_t   mvhp_tensor_bytes(const mvhp_tensor_params_t *t);
+/* The usual normalisation (x / 255 - mean) / std as scale and bias: in double, scale = 1 / (255 std), bias = -mean / std, each
+ * then converted to float.  MVHP_FAILURE for std == 0 and for non-finite input.  A host function. */
+MVHP_EXPORT int      mvhp_tensor_constants(const double mean[3], const double std[3], float scale[3], float bias[3]);
+/* n pictures in d_rgb (3 src_w src_h bytes apart, 4-byte aligned) -> n tensors: picture i at d_out + slot *
+ * mvhp_tensor_bytes(t), slot = d_slots ? d_slots[i] : i (d_slots: device memory; a negative slot skips the picture); d_out is
+ * 16-byte aligned.  n = 0 does nothing.  Refused (MVHP_FAILURE, mvhp_last_error() names the argument) before anything is
+ * launched: parameters mvhp_tensor_bytes refuses, non-finite scale / bias, n < 0, NULL or misaligned pointers.  Asynchronous on
+ * `stream` (NULL = the context's own); nothing is shared between workgroups or launches: safe under stream capture.  More than
+ * 65535 pictures take a second launch. */
+MVHP_EXPORT int      mvhp_tensor_dev(mvhp_ctx_t *ctx, const mvhp_tensor_params_t *t, const uint8_t *d_rgb, int n, void *d_out,
+                                     const int32_t *d_slots /* may be NULL */, void *stream);
+
 /* Page-locked host memory for the host-buffer entry points (H2D / D2H at full PCIe rate). */
 MVHP_EXPORT void *mvhp_host_alloc(size_t bytes);
 MVHP_EXPORT void  mvhp_host_free(void *p);
@@ -704,6 +745,12 @@ MVHP_EXPORT int  mvhp_set_bars_band(mvhp_ctx_t *ctx, int rows);
  * mvhp_plane_hist_dev, 1 ... 65536; 0 (default) = 256, fewer when the grid would leave compute units idle.  It exists so that a
  * test can force band sizes and compare the records: the counts are integers, every value gives the same 3104 bytes. */
 MVHP_EXPORT int  mvhp_set_hist_band(mvhp_ctx_t *ctx, int rows);
+
+/* Test-only knob, like those above (speed only, never results; not meant for products): canvas rows per workgroup of
+ * mvhp_tensor_dev, 1 ... 16384 (cut down to what a workgroup's LDS holds of the source); 0 (default) = about 16 KiB of source and
+ * at most 64 KiB of tensor, fewer when the grid would leave compute units idle.  It exists so that a test can force strip sizes
+ * and compare the bytes: every element is made by one lane from its own sample, every value gives the same tensor. */
+MVHP_EXPORT int  mvhp_set_tensor_rows(mvhp_ctx_t *ctx, int rows);
 
 /* Tuning knob (speed only, never results): waves per picture workgroup, or macroblock rows per band of the banded forms
  * (1, 2, 4, 6, 8, 12 or 16; a layout that is not built for the value takes the next smaller one it is built for, or its
@@ -832,6 +879,26 @@ MVHP_EXPORT void mvhp_engine_destroy(mvhp_engine_t *e);
  * picture can be too big.  d2h_bytes counts the table entries (16 bytes per picture) and the files' bytes.  Not together with
  * MVHP_OUT_JPEG. */
 #define MVHP_OUT_PNG      8
+/* mvhp_engine_decode_ex only (opt-in; "Tensor output" above): the batch's RGB is made exactly as for MVHP_OUT_RGB_ONLY under the
+ * same request (crop, box, aspect, trim, turn and MVHP_OUTPUT_COLOR all apply), mvhp_tensor_dev runs behind it with src_w x src_h
+ * = the geometry's out_w x out_h, and neither planes nor RGB are downloaded.  The parameters are those of the last
+ * mvhp_engine_set_tensor (read at the start of the call; without one the call fails).  canvas 0,0: every tensor has its picture's
+ * size; a picture larger than a non-zero canvas reaches the sink as a failed picture, and decoding goes on.
+ * Host delivery (d_target NULL): only the tensors are downloaded; the sink gets yuv = NULL, rgb = the tensor's bytes and
+ * g->reserved[0] = their length; d2h_bytes grows by exactly mvhp_tensor_bytes per delivered picture.
+ * Device delivery (d_target: device memory of target_pictures tensors, 16-byte aligned): the tensor of picture `seq` is written
+ * straight to d_target + seq * mvhp_tensor_bytes, nothing of the picture is downloaded, and the sink is called with yuv = rgb =
+ * NULL and g->reserved[0] = the length once the batch's kernels have completed.  A failed picture leaves its slot untouched;
+ * seq >= target_pictures fails that picture.  It needs an engine of exactly one context -- the pointer belongs to one device --
+ * and, for the slots to be of one size, a non-zero canvas or pictures of one geometry.
+ * Not together with MVHP_OUT_JPEG, MVHP_OUT_PNG or MVHP_OUTPUT_BARS (g->reserved[0]); composes with MVHP_OUTPUT_SCORE and
+ * MVHP_OUTPUT_HIST. */
+#define MVHP_OUT_TENSOR   16
+typedef struct mvhp_tensor_request {
+    uint32_t canvas_w, canvas_h, dtype, layout, flags, pad_rgb;   /* as in mvhp_tensor_params_t */
+    float scale[3], bias[3];
+    void *d_target; uint32_t target_pictures; uint32_t reserved;  /* reserved: 0 */
+} mvhp_tensor_request_t;
 /* MVHP_OUTPUT_SCORE in mvhp_output_request_t::flags (mvhp_engine_decode_ex only; composes with MVHP_OUTPUT_CROP / _BOX and every
  * output kind above): behind whatever reconstructs the batch (and the deblocking filter, where the stream asks for it)
  * mvhp_luma_stats_dev sums the coded planes over each picture's crop rectangle, the 32-byte records come back with the
@@ -863,6 +930,12 @@ MVHP_EXPORT void mvhp_engine_release_picture(mvhp_engine_t *e, int seq);
 /* MVHP_OUTPUT_HIST: the record of picture `seq` of the running call.  Valid inside the sink call for `seq`, and for a picture the
  * sink kept (verdict 2) until mvhp_engine_release_picture; NULL without the flag, for a failed picture and at any other time. */
 MVHP_EXPORT const mvhp_plane_hist_t *mvhp_engine_picture_hist(mvhp_engine_t *e, int seq);
+/* The tensor request of the MVHP_OUT_TENSOR calls that follow (copied; NULL clears it).  Malformed requests -- what
+ * mvhp_tensor_bytes refuses for a picture of the canvas's size, non-finite scale / bias, reserved != 0, a misaligned d_target or
+ * one without target_pictures -- are refused (MVHP_FAILURE).  Not while a decode call is running. */
+/* The number of device contexts the engine runs (what mvhp_decode_stats_t::contexts reports after a call). */
+MVHP_EXPORT int  mvhp_engine_contexts(mvhp_engine_t *e);
+MVHP_EXPORT int  mvhp_engine_set_tensor(mvhp_engine_t *e, const mvhp_tensor_request_t *t /* NULL clears */);
 
 /* ---- memory placement (MI355X: device memory alternates, in regions of tens of GB, between two halves of the memory
  * system; DESIGN.md 3 "Placement") ---- */

@@ -11,6 +11,10 @@ from .hotpath import (  # noqa: F401
     Engine,
     PlacedBuffers,
     StreamParams,
+    TensorParams,
+    tensor_bytes,
+    tensor_constants,
+    tensor_params,
     MiniVideoError,
     lib,
     lib_path,
@@ -20,4 +24,5 @@ from .hotpath import (  # noqa: F401
     UNSUPPORTED,
 )
 
-__all__ = ["HotPath", "Engine", "PlacedBuffers", "StreamParams", "MiniVideoError", "lib", "lib_path", "MB_BYTES"]
+__all__ = ["HotPath", "Engine", "PlacedBuffers", "StreamParams", "TensorParams", "tensor_bytes", "tensor_constants", "tensor_params",
+           "MiniVideoError", "lib", "lib_path", "MB_BYTES"]

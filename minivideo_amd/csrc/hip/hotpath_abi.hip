@@ -18,6 +18,7 @@
 #include "png_format.h"
 #include "recon_kernels.h"
 #include "represent_policy.h"
+#include "tensor_policy.h"
 
 namespace {
 
@@ -64,6 +65,7 @@ struct mvhp_ctx {
     int          stats_band;  // luma rows per workgroup of the picture-score kernel, 0 = choose (mvhp_set_stats_band)
     int          bars_band;   // luma rows per workgroup of the black-bar counting pass, 0 = choose (mvhp_set_bars_band)
     int          hist_band;   // luma rows per workgroup of the plane-histogram kernel, 0 = choose (mvhp_set_hist_band)
+    int          tensor_rows; // canvas rows per workgroup of the tensor kernel, 0 = choose (mvhp_set_tensor_rows)
     int          n_cus;
     size_t       max_lds;
     int          last_layout, last_waves;   // what the last reconstruction launch used
@@ -245,6 +247,13 @@ MVHP_EXPORT int mvhp_set_bars_band(mvhp_ctx_t *c, int rows)
 {
     if (!c || rows < 0 || rows > 65536) return MVHP_FAILURE;
     c->bars_band = rows;
+    return MVHP_SUCCESS;
+}
+
+MVHP_EXPORT int mvhp_set_tensor_rows(mvhp_ctx_t *c, int rows)
+{
+    if (!c || rows < 0 || rows > 16384) return MVHP_FAILURE;
+    c->tensor_rows = rows;
     return MVHP_SUCCESS;
 }
 
@@ -732,6 +741,45 @@ MVHP_EXPORT int mvhp_plane_hist_dev(mvhp_ctx_t *c, const mvhp_stream_params_t *p
     return MVHP_SUCCESS;
 }
 
+MVHP_EXPORT int mvhp_tensor_dev(mvhp_ctx_t *c, const mvhp_tensor_params_t *t, const uint8_t *d_rgb, int n, void *d_out,
+                                const int32_t *d_slots, void *stream)
+{
+    if (!c || !t) { set_err("mvhp_tensor_dev: no %s", c ? "parameters" : "context"); return MVHP_FAILURE; }
+    if (const char *why = mvtensor::malformed(*t)) { set_err("mvhp_tensor_dev: invalid %s", why); return MVHP_FAILURE; }
+    if (!mvtensor::finite(*t)) { set_err("mvhp_tensor_dev: scale / bias is not finite"); return MVHP_FAILURE; }
+    if (n < 0) { set_err("mvhp_tensor_dev: n = %d", n); return MVHP_FAILURE; }
+    if (!d_rgb || ((uintptr_t)d_rgb & 3)) { set_err("mvhp_tensor_dev: d_rgb is NULL or not 4-byte aligned"); return MVHP_FAILURE; }
+    if (!d_out || ((uintptr_t)d_out & 15)) { set_err("mvhp_tensor_dev: d_out is NULL or not 16-byte aligned"); return MVHP_FAILURE; }
+    if ((uintptr_t)d_slots & 3) { set_err("mvhp_tensor_dev: d_slots is not 4-byte aligned"); return MVHP_FAILURE; }
+    if (n == 0) return MVHP_SUCCESS;
+    HIP_TRY(hipSetDevice(c->device));
+    mvhp::TensorArgs a{};
+    a.src = d_rgb;
+    a.src_end = d_rgb + (size_t)n * 3 * t->src_w * t->src_h;
+    a.n = n;
+    a.sw = (int)t->src_w; a.sh = (int)t->src_h;
+    a.cw = (int)mvtensor::canvas_w(*t); a.ch = (int)mvtensor::canvas_h(*t);
+    a.dtype = (int)t->dtype; a.layout = (int)t->layout; a.bgr = (t->flags & MVHP_TENSOR_BGR) != 0;
+    a.pad_rgb = t->pad_rgb;
+    for (int k = 0; k < 3; k++) { a.scale[k] = t->scale[k]; a.bias[k] = t->bias[k]; }
+    // canvas rows per workgroup: about 16 KiB of source (a row of the widest picture is 48 KiB: one row then) and at most 64 KiB of
+    // tensor, so that several workgroups share a CU; halved while the grid would leave CUs idle -- the rule of the crop copy above.
+    // Speed only: every element is made by one lane from its own sample.
+    const size_t es = mvtensor::element_bytes(t->dtype);
+    int rows = std::max(1, std::min(64, 16384 / (3 * a.sw)));
+    rows = std::min(rows, std::max(1, (int)(65536 / ((size_t)a.cw * 3 * es))));
+    rows = std::min(rows, a.ch);
+    while (rows > 1 && (double)n * ((a.ch + rows - 1) / rows) < 4.0 * c->n_cus) rows = (rows + 1) / 2;
+    // (a forced value, as far as a workgroup's LDS -- 64 KiB -- holds the source rows and 32-bit counts the strip's elements)
+    if (c->tensor_rows > 0) rows = std::max(1, std::min(std::min(c->tensor_rows, a.ch), std::min(4096, (65536 - 64) / (3 * a.sw))));
+    a.rows = rows;
+    a.out = (uint8_t *)d_out;
+    a.tensor_bytes = mvtensor::bytes(*t);
+    a.slots = d_slots;
+    HIP_TRY(mvhp::launch_tensor(a, stream_of(c, stream)));
+    return MVHP_SUCCESS;
+}
+
 MVHP_EXPORT size_t mvhp_jpeg_header_bytes(void) { return MVHP_JPEG_HEADER_BYTES; }
 
 MVHP_EXPORT int mvhp_jpeg_quant_tables(int quality, uint8_t out[128])
@@ -1074,6 +1122,8 @@ int eng_run_batch(DevCtx *d, const mvengine::BatchJob &j, mvengine::BatchDone &d
     if (j.geom && !resample && !j.jpeg && !j.png && !j.color) { err = "reconstruction: an output geometry without an output buffer"; return MVHP_FAILURE; }
     // colour pass: RGB from the final planes -- out_yuv -> out_rgb behind a pass, else d_yuv -> d_rgb at the coded size
     if (j.color && (j.jpeg || !j.geom || (resample ? (!j.out_yuv || !j.out_rgb) : !j.d_rgb))) { err = "reconstruction: invalid colour pass"; return MVHP_FAILURE; }
+    // tensors: from the RGB the job makes -- out_rgb behind a pass, else d_rgb of the coded size
+    if (j.tensor && (j.jpeg || j.png || j.bars || !j.tensor_out || !(resample ? j.out_rgb : j.d_rgb) || (j.slots_host && !j.d_slots))) { err = "reconstruction: invalid tensor output"; return MVHP_FAILURE; }
     ENG_TRY(hipSetDevice(c->device));
     ENG_TRY(hipEventRecord(d->ev[2], c->stream));
     if (mvhp_expand_compact_dev(c, p, j.d_compact, j.stride, j.n, j.d_packed, c->stream) != MVHP_SUCCESS) { err = mvhp_last_error(); return MVHP_FAILURE; }
@@ -1096,6 +1146,11 @@ int eng_run_batch(DevCtx *d, const mvengine::BatchJob &j, mvengine::BatchDone &d
         rc = mvhp_jpeg_encode_dev(c, j.geom, j.jpeg, resample ? j.out_yuv : j.d_yuv, j.n, j.blob, j.blob_cap, j.table, c->stream);
     if (rc == MVHP_SUCCESS && j.png)
         rc = mvhp_png_encode_dev(c, j.geom, j.png, resample ? j.out_rgb : j.d_rgb, j.n, j.blob, j.blob_cap, j.table, c->stream);
+    if (rc == MVHP_SUCCESS && j.tensor) {   // (the slot table rides the job's own queue, in front of the kernel that reads it; the
+        // host copy stays where it is until the wait below)
+        if (j.slots_host) ENG_TRY(hipMemcpyAsync(j.d_slots, j.slots_host, (size_t)j.n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        rc = mvhp_tensor_dev(c, j.tensor, resample ? j.out_rgb : j.d_rgb, j.n, j.tensor_out, j.slots_host ? j.d_slots : nullptr, c->stream);
+    }
     if (rc == MVHP_SUCCESS && j.stats) {
         mvhp_output_geometry_t whole{};   // (no geometry: the rectangle is the coded picture)
         whole.crop_w = whole.out_w = p->width_mbs * 16;
@@ -1166,7 +1221,7 @@ void eng_placed_free(DevCtx *d, void *arena)
 
 const mvengine::DeviceApi g_hip_api = {
     mvhp_device_count, mvhp_host_alloc, mvhp_host_free, eng_ctx_create, eng_ctx_destroy, eng_dev_alloc, eng_dev_free,
-    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_COLOR | mvengine::CAP_PNG | mvengine::CAP_BARS | mvengine::CAP_HIST,
+    eng_dev_free_bytes, eng_h2d, eng_d2h, eng_run_batch, mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_COLOR | mvengine::CAP_PNG | mvengine::CAP_BARS | mvengine::CAP_HIST | mvengine::CAP_TENSOR,
     eng_placed_alloc, eng_placed_free,
 };
 

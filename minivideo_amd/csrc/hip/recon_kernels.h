@@ -209,4 +209,23 @@ struct PlaneHistArgs {
 };
 hipError_t launch_plane_hist(const PlaneHistArgs &a, hipStream_t stream);
 
+// tensor output (tensor_pack.hip): dense RGB8 pictures -> normalised, padded tensors of one shape
+struct TensorArgs {
+    const uint8_t *src;          // the call's pictures, 3 * sw * sh bytes apart, 4-byte aligned
+    const uint8_t *src_end;      // their end: no load reaches outside [src, src_end)
+    int            n;            // pictures first .. first + n of them (launch_tensor splits a call into launches)
+    int            first;
+    int            sw, sh;       // picture
+    int            cw, ch;       // canvas (each >= the picture's side)
+    int            dtype, layout, bgr;
+    uint32_t       pad_rgb;
+    float          scale[3], bias[3];
+    int            rows;         // canvas rows per workgroup: tensor_lds_bytes(rows, sw) must fit a workgroup's LDS (64 KiB)
+    uint8_t       *out;          // 16-byte aligned; a picture's tensor is tensor_bytes long
+    size_t         tensor_bytes;
+    const int32_t *slots;        // NULL: picture i of the call goes to slot i
+};
+size_t     tensor_lds_bytes(int rows, int sw);
+hipError_t launch_tensor(const TensorArgs &a, hipStream_t stream);
+
 } // namespace mvhp

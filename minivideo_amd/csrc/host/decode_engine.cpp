@@ -33,6 +33,7 @@
 #include "h264_frontend.h"
 #include "png_format.h"
 #include "stream_internal.h"
+#include "tensor_policy.h"
 
 namespace mvengine {
 
@@ -154,6 +155,8 @@ enum BufKind {
     kJpegTab,    // ... and table of a batch
     kStats,      // MVHP_OUTPUT_SCORE or MVHP_OUTPUT_BARS (never both): the records of a batch (n x 32 bytes)
     kHist,       // MVHP_OUTPUT_HIST: the plane histograms of a batch (n x 3104 bytes)
+    kTensor,     // MVHP_OUT_TENSOR, host delivery: the tensors of a batch (what is downloaded then)
+    kSlots,      // MVHP_OUT_TENSOR, device delivery: the slot numbers of a batch (n x 4 bytes; the tensors go to the caller's memory)
     kBufKinds,
     kArenaKinds = kOutYuv,
 };
@@ -196,7 +199,11 @@ struct Wants {
     bool bars = false;              // MVHP_OUTPUT_BARS (it changes no picture and no path; never beside score, jpeg or png)
     int bars_level = MVHP_BARS_LEVEL_DEFAULT;
     bool hist = false;              // MVHP_OUTPUT_HIST (it changes no picture and no path; never beside bars)
+    bool tensor = false;            // MVHP_OUT_TENSOR: the RGB is made as for `rgb` alone (which is set) and packed into tensors of
+    mvhp_tensor_request_t treq{};   // this request; only those are delivered.  Never beside jpeg, png or bars
 };
+// the tensor of a picture of the delivered geometry g under a call's request
+mvhp_tensor_params_t tensor_params(const Wants &w, const mvhp_output_geometry_t &g) { return mvtensor::of_request(w.treq, g.out_w, g.out_h); }
 // whether a batch of the DELIVERED geometry g, turned by `turns`, has a resample pass in front of the turn
 bool scales_before_turn(const mvhp_output_geometry_t &g, int turns)
 {
@@ -230,6 +237,8 @@ size_t picture_bytes(BufKind k, const mvhp_stream_params_t &p, const mvhp_output
     case kJpegTab:  return w.jpeg || w.png ? sizeof(mvhp_jpeg_entry_t) : 0;
     case kStats:    return w.score ? sizeof(mvhp_luma_stats_t) : w.bars ? sizeof(mvhp_luma_bars_t) : 0;
     case kHist:     return w.hist ? sizeof(mvhp_plane_hist_t) : 0;
+    case kTensor:   return w.tensor && !w.treq.d_target ? mvtensor::bytes(tensor_params(w, g)) : 0;
+    case kSlots:    return w.tensor && w.treq.d_target ? sizeof(int32_t) : 0;
     default:        return 0;
     }
 }
@@ -334,7 +343,10 @@ private:
 public:
     void release_picture(int seq);   // any thread
     const mvhp_plane_hist_t *picture_hist(int seq);   // any thread
+    int set_tensor(const mvhp_tensor_request_t *t, std::string &err);   // between decode calls
+    int contexts() const { return (int)ctx_.size(); }
 private:
+    bool tensor_fits(int seq, const mvhp_output_geometry_t &g, std::string &why);   // MVHP_OUT_TENSOR: may picture `seq` be issued
     bool grow(Pinned &p, size_t need);   // no lock needed
     int launch_cap(size_t per_picture) const;
     int batch_capacity(const mvhp_stream_params_t &p, const mvhp_output_geometry_t &g, bool use_geom, int remaining) const;
@@ -362,6 +374,9 @@ private:
     Wants w_;                                   // (score: taken out of req_.flags)
     mvhp_jpeg_params_t jpeg_{};
     mvhp_png_params_t png_{};
+    mvhp_tensor_request_t tensor_req_{};        // mvhp_engine_set_tensor: what the next MVHP_OUT_TENSOR call copies into w_ ...
+    bool have_tensor_req_ = false;              // ... if there is one
+    size_t tensor_slot_bytes_ = 0;   // device delivery: the size of the target's slots, the first issued picture's tensor (0: none yet)
     int color_mode_ = 0;             // MVHP_OUTPUT_COLOR_MODE of the call
     mvhp_color_params_t picture_color(int idr, const mvhp_stream_params_t &p, const mvhp_output_geometry_t &g) const;
     mvhp_output_request_t req_{};               // flags 0: pictures of the coded size
@@ -611,7 +626,8 @@ bool Engine::ensure_devbuf(Ctx &c, DevBuf &b, const Batch &bt, std::string &err)
     static const struct { const char *of, *unit; } what[kBufKinds] = {
         {"", " pictures"}, {"", " pictures"}, {"", " pictures"}, {"", " pictures"}, {"the output pictures of ", ""}, {"the output pictures of ", ""},
         {"the unturned pictures of ", ""},
-        {"the JPEG files of ", ""}, {"the JPEG files of ", ""}, {"the picture scores of ", ""}, {"the plane histograms of ", ""}};
+        {"the JPEG files of ", ""}, {"the JPEG files of ", ""}, {"the picture scores of ", ""}, {"the plane histograms of ", ""},
+        {"the tensors of ", ""}, {"the tensor slots of ", ""}};
     const bool job_shape = bt.params.width_mbs == job_params_.width_mbs && bt.params.height_mbs == job_params_.height_mbs;
     for (int k = 0; k < kBufKinds; k++) {
         if (k < kArenaKinds && b.arena_piece) continue;   // (checked above; never grown one by one)
@@ -659,6 +675,32 @@ void Engine::close_batch(Batch *b)
     }
 }
 
+// MVHP_OUT_TENSOR: a picture of the delivered geometry g has a tensor of the request's canvas and, with device delivery, a slot of
+// the target: slot `seq`, every slot of one size -- the canvas's, or with canvas 0 the first issued picture's.
+bool Engine::tensor_fits(int seq, const mvhp_output_geometry_t &g, std::string &why)
+{
+    if (!w_.tensor) return true;
+    const mvhp_tensor_params_t t = tensor_params(w_, g);
+    const size_t tb = mvtensor::bytes(t);
+    if (!tb) {
+        why = "the picture (" + std::to_string(g.out_w) + " x " + std::to_string(g.out_h) + ") does not fit the tensor canvas (" +
+              std::to_string(t.canvas_w) + " x " + std::to_string(t.canvas_h) + ")";
+        return false;
+    }
+    if (!w_.treq.d_target) return true;
+    if ((uint32_t)seq >= w_.treq.target_pictures) {
+        why = "picture " + std::to_string(seq) + " is past the tensor target's " + std::to_string(w_.treq.target_pictures) + " slots";
+        return false;
+    }
+    if (!tensor_slot_bytes_) tensor_slot_bytes_ = tb;
+    if (tb != tensor_slot_bytes_) {
+        why = "device delivery without a canvas: the picture's tensor (" + std::to_string(tb) + " bytes) is not of the slots' size (" +
+              std::to_string(tensor_slot_bytes_) + ")";
+        return false;
+    }
+    return true;
+}
+
 void Engine::feeder()
 {
     std::unique_lock<std::mutex> l(mu_);
@@ -693,8 +735,9 @@ void Engine::feeder()
         bool use0 = false;
         {
             std::string why;
-            if (!picture_geometry(order_[first_seq], p0, g0, use0, why)) {
-                // a picture whose geometry cannot be formed (the crop leaves nothing) fails without occupying a slot
+            if (!picture_geometry(order_[first_seq], p0, g0, use0, why) || !tensor_fits(first_seq, g0, why)) {
+                // a picture whose geometry cannot be formed (the crop leaves nothing), or whose tensor has no place (larger than
+                // the canvas, past the target's last slot), fails without occupying a slot
                 PicResult &r = results_[(size_t)first_seq];
                 r.rc = MVHP_FAILURE;
                 r.err = why;
@@ -738,6 +781,7 @@ void Engine::feeder()
             bool ui = false;
             std::string why;
             if (!picture_geometry(order_[seq_at(same)], pi, gi, ui, why) || !same_geometry(gi, g0)) break;
+            if (!tensor_fits(seq_at(same), gi, why)) break;   // (it fails as the first picture of the next round)
             if (!same_color(picture_color(order_[seq_at(same)], pi, gi), c0)) break;
             same++;
         }
@@ -1039,6 +1083,22 @@ void Engine::launcher(int k)
             job.bars = w_.bars ? (mvhp_luma_bars_t *)buf(kStats) : nullptr;
             job.bars_level = w_.bars_level;
             job.hist = w_.hist ? (mvhp_plane_hist_t *)buf(kHist) : nullptr;
+            const mvhp_tensor_params_t tensor = tensor_params(w_, b->geom);
+            std::vector<int32_t> slots;
+            if (w_.tensor) {
+                job.tensor = &tensor;
+                job.tensor_out = w_.treq.d_target ? w_.treq.d_target : (void *)buf(kTensor);
+                if (w_.treq.d_target) {   // picture `seq` into slot `seq`; a picture that failed to parse (final by now) into none
+                    slots.resize((size_t)b->total);
+                    std::lock_guard<std::mutex> l(mu_);
+                    for (int i = 0; i < b->total; i++) {
+                        const PicResult &r = results_[(size_t)b->seqs[(size_t)i]];
+                        slots[(size_t)i] = r.parsed_ok && !r.ready ? b->seqs[(size_t)i] : -1;
+                    }
+                    job.slots_host = slots.data();
+                    job.d_slots = (int32_t *)buf(kSlots);
+                }
+            }
             rc = api_.run_batch(cx.dev, job, done, err);
         }
         const float ms = done.ms;
@@ -1091,6 +1151,24 @@ const mvhp_plane_hist_t *Engine::picture_hist(int seq)
     return r.hist;
 }
 
+int Engine::set_tensor(const mvhp_tensor_request_t *t, std::string &err)
+{
+    std::lock_guard<std::mutex> l(mu_);
+    if (s_) { err = "mvhp_engine_set_tensor: a decode call is running"; return MVHP_FAILURE; }
+    if (!t) { have_tensor_req_ = false; tensor_req_ = mvhp_tensor_request_t{}; return MVHP_SUCCESS; }
+    // (judged for a picture that fills the canvas -- one sample where there is none -- every picture is judged again when it is issued)
+    const mvhp_tensor_params_t p = mvtensor::of_request(*t, t->canvas_w ? t->canvas_w : 1, t->canvas_h ? t->canvas_h : 1);
+    const char *why = mvtensor::malformed(p);
+    if (!why && !mvtensor::finite(p)) why = "scale / bias (not finite)";
+    if (!why && t->reserved) why = "reserved (must be 0)";
+    if (!why && ((uintptr_t)t->d_target & 15)) why = "d_target (not 16-byte aligned)";
+    if (!why && t->d_target && !t->target_pictures) why = "target_pictures (0 with a device target)";
+    if (why) { err = std::string("mvhp_engine_set_tensor: invalid ") + why; return MVHP_FAILURE; }
+    tensor_req_ = *t;
+    have_tensor_req_ = true;
+    return MVHP_SUCCESS;
+}
+
 void Engine::put_out(OutChunk *oc)
 {
     free_out_.push_back(oc);
@@ -1110,9 +1188,12 @@ void Engine::downloader(int k)
         }
         // what comes back, from where, how many bytes per picture (a batch with a geometry: only its output pictures)
         const BufKind ky = planes_kind(b->use_geom), kr = rgb_kind(b->use_geom);
-        const size_t yb = w_.yuv ? need(*b, ky) : 0, rb = w_.rgb ? need(*b, kr) : 0, sb = need(*b, kStats);
+        // (MVHP_OUT_TENSOR: the tensors take the place of the RGB -- the batch's own with host delivery, none with device delivery,
+        //  where the pictures are in the caller's memory already: the batch's kernels have completed)
+        const size_t yb = w_.yuv ? need(*b, ky) : 0, rb = w_.tensor ? need(*b, kTensor) : w_.rgb ? need(*b, kr) : 0, sb = need(*b, kStats);
         const size_t hb = need(*b, kHist);
-        const uint8_t *d_y = b->buf->m[ky].p, *d_r = b->buf->m[kr].p, *d_s = b->buf->m[kStats].p, *d_h = b->buf->m[kHist].p;
+        const uint32_t tensor_len = w_.tensor ? (uint32_t)std::min<size_t>(mvtensor::bytes(tensor_params(w_, b->geom)), UINT32_MAX) : 0;
+        const uint8_t *d_y = b->buf->m[ky].p, *d_r = b->buf->m[w_.tensor ? kTensor : kr].p, *d_s = b->buf->m[kStats].p, *d_h = b->buf->m[kHist].p;
         const int C = std::min(chunk_pictures(b->params), b->capacity);
         std::string fail;
         for (int g = 0; g < b->total && fail.empty(); g += C) {
@@ -1237,7 +1318,7 @@ void Engine::downloader(int k)
                 if (rb) { dst[np] = oc->rgb.p; src[np] = d_r + (size_t)g * rb; nb[np++] = (size_t)n * rb; }
                 if (sb) { dst[np] = oc->stats.p; src[np] = d_s + (size_t)g * sb; nb[np++] = score_bytes; }
                 if (hb) { dst[np] = oc->hist.p; src[np] = d_h + (size_t)g * hb; nb[np++] = hist_bytes; }
-                ok = api_.d2h(cx.dev, np, dst, src, nb, &ms, err) == MVHP_SUCCESS;
+                ok = np == 0 || api_.d2h(cx.dev, np, dst, src, nb, &ms, err) == MVHP_SUCCESS;   // (np 0: tensors delivered on the device)
             }
             {
                 std::lock_guard<std::mutex> l(mu_);
@@ -1258,6 +1339,7 @@ void Engine::downloader(int k)
                             r.geom.reserved[1] = boxes[i].w | boxes[i].h << 16;
                         }
                         if (hists) r.hist = hists + i;
+                        if (w_.tensor) r.geom.reserved[0] = tensor_len;
                         r.ready = true;
                         oc->refs++;
                     }
@@ -1303,6 +1385,16 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
                    : "MVHP_OUT_PNG and MVHP_OUT_JPEG are two output kinds: a call delivers one";
         return MVHP_FAILURE;
     }
+    if (out_mask & MVHP_OUT_TENSOR) {   // (the tensor's length travels in g->reserved[0], as a file's length does)
+        const char *why = sink ? "MVHP_OUT_TENSOR needs mvhp_engine_decode_ex: its sink gets the tensor's length with the geometry"
+                          : (out_mask & MVHP_OUT_JPEG) ? "MVHP_OUT_TENSOR and MVHP_OUT_JPEG are two output kinds: a call delivers one"
+                          : (out_mask & MVHP_OUT_PNG) ? "MVHP_OUT_TENSOR and MVHP_OUT_PNG are two output kinds: a call delivers one"
+                          : (req && (req->flags & MVHP_OUTPUT_BARS)) ? "MVHP_OUTPUT_BARS and MVHP_OUT_TENSOR both use g->reserved[0]: a call delivers one"
+                          : !have_tensor_req_ ? "MVHP_OUT_TENSOR without a tensor request: mvhp_engine_set_tensor comes first"
+                          : !(api_.caps & CAP_TENSOR) ? "this device table has no tensor operation"
+                          : (tensor_req_.d_target && ctx_.size() != 1) ? "MVHP_OUT_TENSOR with a device target needs an engine of exactly one context: the pointer belongs to one device" : nullptr;
+        if (why) { err = why; return MVHP_FAILURE; }
+    }
     if (req && (req->flags & MVHP_OUTPUT_BARS)) {   // the box travels in the two words that are the file length and the score elsewhere
         const char *why = sink ?"MVHP_OUTPUT_BARS needs mvhp_engine_decode_ex: its sink gets the box with the geometry"
                           : (out_mask & MVHP_OUT_JPEG) ? "MVHP_OUTPUT_BARS and MVHP_OUT_JPEG both use g->reserved[0]: a call delivers one"
@@ -1323,8 +1415,11 @@ int Engine::decode(const mvhp_stream &s, const int *order, int n_order, int want
         s_ = &s; order_ = order; n_order_ = n_order; wanted_ = std::min(wanted, n_order);
         w_.jpeg = (out_mask & MVHP_OUT_JPEG) != 0;
         w_.png = (out_mask & MVHP_OUT_PNG) != 0;
-        w_.rgb = !w_.jpeg && !w_.png && (out_mask & 1) != 0;
-        w_.yuv = !w_.jpeg && !w_.png && (!w_.rgb || (out_mask & 2) == 0);
+        w_.tensor = (out_mask & MVHP_OUT_TENSOR) != 0;
+        w_.treq = w_.tensor ? tensor_req_ : mvhp_tensor_request_t{};
+        tensor_slot_bytes_ = 0;
+        w_.rgb = !w_.jpeg && !w_.png && ((out_mask & 1) != 0 || w_.tensor);   // (a tensor call makes its RGB as MVHP_OUT_RGB_ONLY does)
+        w_.yuv = !w_.jpeg && !w_.png && !w_.tensor && (!w_.rgb || (out_mask & 2) == 0);
         jpeg_ = mvhp_jpeg_params_t{};
         if (w_.jpeg) {   // mvhp_output_request_t::reserved carries the encoder's parameters
             const uint32_t rsv = req ? req->reserved : 0;
@@ -1499,6 +1594,12 @@ Engine *engine_create(const DeviceApi &api, const mvhp_engine_opts_t *opts, std:
 
 void engine_destroy(Engine *e) { delete e; }
 void engine_release_picture(Engine *e, int seq) { e->release_picture(seq); }
+int engine_contexts(Engine *e) { return e ? e->contexts() : 0; }
+int engine_set_tensor(Engine *e, const mvhp_tensor_request_t *t, std::string &err)
+{
+    if (!e) { err = "no engine"; return MVHP_FAILURE; }
+    return e->set_tensor(t, err);
+}
 const mvhp_plane_hist_t *engine_picture_hist(Engine *e, int seq) { return e ? e->picture_hist(seq) : nullptr; }
 
 int engine_decode(Engine *e, const mvhp_stream &s, const int *order, int n_order, int wanted, int out_mask,
@@ -1548,6 +1649,16 @@ MVHP_EXPORT void mvhp_engine_release_picture(mvhp_engine_t *h, int seq)
 MVHP_EXPORT const mvhp_plane_hist_t *mvhp_engine_picture_hist(mvhp_engine_t *h, int seq)
 {
     return h ? mvengine::engine_picture_hist(h->e, seq) : nullptr;
+}
+
+MVHP_EXPORT int mvhp_engine_contexts(mvhp_engine_t *h) { return h ? mvengine::engine_contexts(h->e) : 0; }
+
+MVHP_EXPORT int mvhp_engine_set_tensor(mvhp_engine_t *h, const mvhp_tensor_request_t *t)
+{
+    if (!h) return MVHP_FAILURE;
+    const int rc = mvengine::engine_set_tensor(h->e, t, g_engine_err);
+    if (rc != MVHP_SUCCESS) fprintf(stderr, "[minivideo] %s\n", g_engine_err.c_str());
+    return rc;
 }
 
 MVHP_EXPORT int mvhp_engine_decode(mvhp_engine_t *h, const mvhp_stream_t *s, const int *order, int n_order, int wanted,

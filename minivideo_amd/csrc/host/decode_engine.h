@@ -54,6 +54,11 @@ struct BatchJob {
     int bars_level;             // same planes -> n records (never beside `stats`, `jpeg` or `png`)
     mvhp_plane_hist_t *hist;    // NULL: no plane histograms.  Else mvhp_plane_hist_dev over the same rectangle of the same planes ->
                                 // n records of 3104 bytes, 16-byte aligned (beside anything but `bars`)
+    const mvhp_tensor_params_t *tensor;   // NULL: no tensors.  Else mvhp_tensor_dev of the n RGB pictures the job makes -- out_rgb where a
+    void *tensor_out;                     // pass behind the reconstruction wrote it, else d_rgb; src_w x src_h is their size -- into
+    const int32_t *slots_host;            // tensor_out (16-byte aligned).  slots_host NULL: picture i into slot i of tensor_out; else
+    int32_t *d_slots;                     // n slot numbers in HOST memory (negative: the picture is skipped), which the job copies to
+                                          // d_slots (device, n x 4 bytes) on its queue first.  Never beside `jpeg`, `png` or `bars`
 };
 struct BatchDone {
     float ms;            // device-side duration of the whole job, one bracketed interval
@@ -61,7 +66,7 @@ struct BatchDone {
 };
 
 // what run_batch can do beyond pictures of the coded size; a job that needs a missing bit fails in the engine, with a message
-enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4, CAP_ORIENT = 8, CAP_PNG = 16, CAP_COLOR = 32, CAP_BARS = 64, CAP_HIST = 128 };
+enum : uint32_t { CAP_GEOMETRY = 1, CAP_JPEG = 2, CAP_SCORE = 4, CAP_ORIENT = 8, CAP_PNG = 16, CAP_COLOR = 32, CAP_BARS = 64, CAP_HIST = 128, CAP_TENSOR = 256 };
 
 // Every operation blocks its calling thread until the device has finished it; the engine runs one thread per queue
 // and context, which is what overlaps upload(k+1), kernel(k) and download(k-1).  *ms = device-side duration.
@@ -92,6 +97,9 @@ Engine *engine_create(const DeviceApi &api, const mvhp_engine_opts_t *opts, std:
 void    engine_destroy(Engine *e);
 void    engine_release_picture(Engine *e, int seq);
 const mvhp_plane_hist_t *engine_picture_hist(Engine *e, int seq);   // mvhp_engine_picture_hist (include/minivideo_hotpath.h)
+// mvhp_engine_set_tensor (include/minivideo_hotpath.h): t NULL clears; a malformed request is refused with a message
+int     engine_set_tensor(Engine *e, const mvhp_tensor_request_t *t, std::string &err);
+int     engine_contexts(Engine *e);   // mvhp_engine_contexts
 int     effective_cores();   // hardware threads cut down to the container's CPU quota
 // one of sink / sink_ex (or neither); req NULL or flags 0: pictures of the coded size, the path without a geometry pass
 int     engine_decode(Engine *e, const mvhp_stream &s, const int *order, int n_order, int wanted, int out_mask,

@@ -13,6 +13,7 @@
 #include "h264_frontend.h"
 #include "mp4_demux.h"
 #include "stream_internal.h"
+#include "tensor_policy.h"
 
 using namespace h264;
 
@@ -468,6 +469,13 @@ MVHP_EXPORT size_t mvhp_geometry_yuv_bytes(const mvhp_output_geometry_t *g)
 MVHP_EXPORT size_t mvhp_geometry_rgb_bytes(const mvhp_output_geometry_t *g)
 {
     return g ? (size_t)g->out_w * g->out_h * 3 : 0;
+}
+
+MVHP_EXPORT size_t mvhp_tensor_bytes(const mvhp_tensor_params_t *t) { return t ? mvtensor::bytes(*t) : 0; }
+
+MVHP_EXPORT int mvhp_tensor_constants(const double mean[3], const double std[3], float scale[3], float bias[3])
+{
+    return mvtensor::constants(mean, std, scale, bias) ? MVHP_SUCCESS : MVHP_FAILURE;
 }
 
 MVHP_EXPORT int mvhp_stream_decode_packed(const mvhp_stream_t *s, int idr, void *packed, size_t packed_bytes)

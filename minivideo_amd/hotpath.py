@@ -56,6 +56,7 @@ class StreamParams(C.Structure):
 
 OUT_JPEG = 4                                                            # mvhp_engine_decode_ex output kind (MVHP_OUT_JPEG)
 OUT_PNG = 8                                                             # ... (MVHP_OUT_PNG)
+OUT_TENSOR = 16                                                         # ... (MVHP_OUT_TENSOR; Engine.set_tensor())
 OUTPUT_CROP, OUTPUT_BOX, OUTPUT_SCORE = 1, 2, 4                          # mvhp_output_request_t flags (MVHP_OUTPUT_*)
 OUTPUT_ORIENT, OUTPUT_ROTATE_SHIFT = 8, 4                                # ... the stream's own rotation; bits 4-5: further turns
 OUTPUT_ASPECT, OUTPUT_COLOR, OUTPUT_COLOR_MODE_SHIFT = 0x800, 0x80, 8     # ... square samples; RGB by a colour pass, bits 8-10: its mode
@@ -249,6 +250,67 @@ def represent_choose(hists, eligible=None):
             raise ValueError("one eligibility flag per record")
         el = (C.c_uint8 * max(a.size, 1))(*[1 if x else 0 for x in eligible])
     return int(lib().mvhp_represent_choose(a.ctypes.data if a.size else None, int(a.size), el))
+
+
+TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2                           # mvhp_tensor_params_t::dtype (MVHP_TENSOR_*)
+TENSOR_NCHW, TENSOR_NHWC = 0, 1                                         # ... ::layout
+TENSOR_BGR = 1                                                          # ... ::flags
+TENSOR_DTYPES = ("float32", "float16", "bfloat16")
+TENSOR_LAYOUTS = ("nchw", "nhwc")
+
+
+class TensorParams(C.Structure):
+    """mvhp_tensor_params_t: dense RGB8 pictures of src_w x src_h -> tensors of canvas_h x canvas_w (0, 0 = the picture's size)"""
+    _fields_ = [("src_w", C.c_uint32), ("src_h", C.c_uint32), ("canvas_w", C.c_uint32), ("canvas_h", C.c_uint32),
+                ("dtype", C.c_uint32), ("layout", C.c_uint32), ("flags", C.c_uint32), ("pad_rgb", C.c_uint32),
+                ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+class TensorRequest(C.Structure):
+    """mvhp_tensor_request_t: what Engine.set_tensor() hands to the MVHP_OUT_TENSOR calls that follow"""
+    _fields_ = [("canvas_w", C.c_uint32), ("canvas_h", C.c_uint32), ("dtype", C.c_uint32), ("layout", C.c_uint32),
+                ("flags", C.c_uint32), ("pad_rgb", C.c_uint32), ("scale", C.c_float * 3), ("bias", C.c_float * 3),
+                ("d_target", C.c_void_p), ("target_pictures", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def _tensor_code(value, names, what):
+    if isinstance(value, int):
+        return value
+    name = str(value).replace("torch.", "").lower()
+    if name not in names:
+        raise ValueError("%s %r (one of %s)" % (what, value, ", ".join(names)))
+    return names.index(name)
+
+
+def tensor_params(src_w, src_h, canvas=None, dtype="float32", layout="nchw", bgr=False, pad=(0, 0, 0), scale=(1.0, 1.0, 1.0),
+                  bias=(0.0, 0.0, 0.0)):
+    """a TensorParams: canvas = (w, h) or None for the picture's size; dtype a name of TENSOR_DTYPES (or a torch dtype), layout
+    a name of TENSOR_LAYOUTS; pad = the (r, g, b) of the canvas outside the picture; scale, bias per R, G, B"""
+    t = TensorParams()
+    t.src_w, t.src_h = int(src_w), int(src_h)
+    t.canvas_w, t.canvas_h = (int(canvas[0]), int(canvas[1])) if canvas else (0, 0)
+    t.dtype = _tensor_code(dtype, TENSOR_DTYPES, "tensor dtype")
+    t.layout = _tensor_code(layout, TENSOR_LAYOUTS, "tensor layout")
+    t.flags = TENSOR_BGR if bgr else 0
+    t.pad_rgb = (int(pad[0]) & 255) << 16 | (int(pad[1]) & 255) << 8 | (int(pad[2]) & 255)
+    for k in range(3):
+        t.scale[k], t.bias[k] = scale[k], bias[k]
+    return t
+
+
+def tensor_bytes(params):
+    """mvhp_tensor_bytes: bytes of one picture's tensor, 0 for malformed parameters (no device needed)"""
+    return int(lib().mvhp_tensor_bytes(C.byref(params)))
+
+
+def tensor_constants(mean, std):
+    """mvhp_tensor_constants: (scale, bias), two float32 arrays of three, for (x / 255 - mean) / std per R, G, B (no device
+    needed); ValueError for std == 0 or non-finite input"""
+    m, s = (C.c_double * 3)(*[float(x) for x in mean]), (C.c_double * 3)(*[float(x) for x in std])
+    scale, bias = (C.c_float * 3)(), (C.c_float * 3)()
+    if lib().mvhp_tensor_constants(m, s, scale, bias) != SUCCESS:
+        raise ValueError("tensor_constants: std must not be 0 and mean, std must be finite")
+    return np.array(scale[:], np.float32), np.array(bias[:], np.float32)
 
 
 class LumaBars(C.Structure):
@@ -515,6 +577,14 @@ def lib():
     L.mvhp_plane_hist_dev.argtypes = [vp, pp, pg, vp, i32, vp, vp]
     L.mvhp_set_hist_band.restype = i32
     L.mvhp_set_hist_band.argtypes = [vp, i32]
+    L.mvhp_tensor_bytes.restype = sz
+    L.mvhp_tensor_bytes.argtypes = [C.POINTER(TensorParams)]
+    L.mvhp_tensor_constants.restype = i32
+    L.mvhp_tensor_constants.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.mvhp_tensor_dev.restype = i32
+    L.mvhp_tensor_dev.argtypes = [vp, C.POINTER(TensorParams), vp, i32, vp, vp, vp]
+    L.mvhp_set_tensor_rows.restype = i32
+    L.mvhp_set_tensor_rows.argtypes = [vp, i32]
     pb = C.POINTER(LumaBars)
     L.mvhp_bars_need.restype = u32
     L.mvhp_bars_need.argtypes = [u32]
@@ -678,6 +748,18 @@ class HotPath:
         rc = self._L.mvhp_plane_hist_dev(self._h, C.byref(params), C.byref(geom), d_yuv_coded, int(n), d_hist, stream)
         if rc != SUCCESS:
             raise _err(self._L, "mvhp_plane_hist_dev")
+
+    def tensor_dev(self, params, d_rgb, n, d_out, slots=None, stream=None):
+        """n dense RGB8 pictures (device, 4-byte aligned) -> n tensors of tensor_bytes(params) at d_out (device, 16-byte aligned):
+        picture i in slot slots[i] (a device pointer to n int32; negative = skipped), or in slot i.  Asynchronous."""
+        rc = self._L.mvhp_tensor_dev(self._h, C.byref(params) if params is not None else None, d_rgb, int(n), d_out, slots, stream)
+        if rc != SUCCESS:
+            raise _err(self._L, "mvhp_tensor_dev")
+
+    def set_tensor_rows(self, rows):
+        """test-only: canvas rows per workgroup of tensor_dev, 0 = choose (speed only: the tensors do not depend on it)"""
+        if self._L.mvhp_set_tensor_rows(self._h, int(rows)) != SUCCESS:
+            raise MiniVideoError("mvhp_set_tensor_rows(%d) failed" % rows)
 
     def set_hist_band(self, rows):
         """test-only: luma rows per workgroup of plane_hist_dev, 0 = choose (speed only: the records do not depend on it)"""
@@ -848,6 +930,11 @@ class Engine:
         L.mvhp_engine_release_picture.argtypes = [C.c_void_p, C.c_int]
         L.mvhp_engine_picture_hist.restype = C.c_void_p
         L.mvhp_engine_picture_hist.argtypes = [C.c_void_p, C.c_int]
+        L.mvhp_engine_contexts.restype = C.c_int
+        L.mvhp_engine_contexts.argtypes = [C.c_void_p]
+        self._device = int(first_device)
+        L.mvhp_engine_set_tensor.restype = C.c_int
+        L.mvhp_engine_set_tensor.argtypes = [C.c_void_p, C.POINTER(TensorRequest)]
         o = EngineOpts(contexts, host_threads, batch_pictures, chunk_pictures, fail_context, first_device)
         o.reserved[0] = 1 if placed else 0   # bit 0: batch buffers from mvhp_placed_alloc_sets (same as MINIVIDEO_PLACED=1)
         h = C.c_void_p()
@@ -879,8 +966,75 @@ class Engine:
             return None
         return np.frombuffer(C.string_at(p, PLANE_HIST_DTYPE.itemsize), PLANE_HIST_DTYPE)[0].copy()
 
+    def set_tensor(self, canvas=None, dtype="float32", layout="nchw", bgr=False, pad=(0, 0, 0), scale=(1.0, 1.0, 1.0),
+                   bias=(0.0, 0.0, 0.0), d_target=None, target_pictures=0, clear=False):
+        """mvhp_engine_set_tensor: the tensors of the decode(tensor=True) calls that follow (the arguments of tensor_params();
+        canvas None = every tensor has its picture's size).  d_target = a device pointer to target_pictures tensors (16-byte
+        aligned): device delivery, picture seq straight into slot seq, on an engine of one context.  clear=True takes the
+        request back.  MiniVideoError for a request the library refuses."""
+        if clear:
+            self._L.mvhp_engine_set_tensor(self._h, None)
+            return
+        t = tensor_params(1, 1, None, dtype, layout, bgr, pad, scale, bias)
+        r = TensorRequest()
+        r.canvas_w, r.canvas_h = (int(canvas[0]), int(canvas[1])) if canvas else (0, 0)
+        r.dtype, r.layout, r.flags, r.pad_rgb = t.dtype, t.layout, t.flags, t.pad_rgb
+        for k in range(3):
+            r.scale[k], r.bias[k] = t.scale[k], t.bias[k]
+        r.d_target, r.target_pictures = d_target, int(target_pictures)
+        if self._L.mvhp_engine_set_tensor(self._h, C.byref(r)) != SUCCESS:
+            raise MiniVideoError("mvhp_engine_set_tensor refused the request (see the message on stderr)")
+
+    @property
+    def contexts(self):
+        """mvhp_engine_contexts: the number of device contexts the engine runs"""
+        return int(self._L.mvhp_engine_contexts(self._h))
+
+    def decode_tensors(self, stream_handle, order, size=None, dtype=None, layout="nchw", mean=(0, 0, 0), std=(1, 1, 1), pad=(0, 0, 0),
+                       bgr=False, output=None, rotate=None, aspect=False, color=None, trim=False):
+        """The pictures order[...] as one normalised batch tensor that never leaves the device -> (tensor, ok).
+        tensor: a torch.Tensor on the engine's device, [len(order), 3, h, w] (layout "nchw") or [len(order), h, w, 3] ("nhwc"), of
+        dtype torch.float16 (the default), torch.float32 or torch.bfloat16 (or their names): (x / 255 - mean) / std per R, G, B
+        (bgr=True: channel order B, G, R), under the contract of mvhp_tensor_dev.  size = (w, h): every picture is fitted into
+        that box (output=None: the box is `size`; pictures are never enlarged) and centred on a canvas of that size filled with
+        `pad` = (r, g, b); size=None: the tensor has the pictures' own size, which must be one size.  output, rotate, aspect,
+        color and trim are decode()'s.  ok: one boolean per picture; the slot of a picture that failed (or does not fit) is zero.
+        Device delivery: ValueError on an engine of more than one context."""
+        import torch
+        if self.contexts != 1:
+            raise ValueError("decode_tensors writes into one device's memory: the engine must have exactly one context (has %d)" % self.contexts)
+        code = _tensor_code(dtype if dtype is not None else "float16", TENSOR_DTYPES, "tensor dtype")
+        lay = _tensor_code(layout, TENSOR_LAYOUTS, "tensor layout")
+        if size is not None and output is None:
+            output = (int(size[0]), int(size[1]))
+        if size is not None:
+            w, h = int(size[0]), int(size[1])
+        else:
+            g = output_geometry(stream_handle, order[0], output, rotate, aspect, trim) if len(order) else None
+            if g is None:
+                raise ValueError("decode_tensors without a size: the first picture has no geometry to take it from")
+            w, h = g.out_w, g.out_h
+        n = len(order)
+        shape = (n, 3, h, w) if lay == TENSOR_NCHW else (n, h, w, 3)
+        out = torch.zeros(shape, dtype=getattr(torch, TENSOR_DTYPES[code]), device=torch.device("cuda", self._device))
+        ok = [False] * n
+        scale, bias = tensor_constants(mean, std)
+
+        def sink(seq, idr, rc, err, p, g, yuv, rgb):
+            ok[seq] = rc == SUCCESS
+            return 1 if rc == SUCCESS else 0
+
+        torch.cuda.synchronize(out.device)   # (the zeros are there before the engine's own queue writes over them)
+        self.set_tensor((w, h) if size is not None else None, code, lay, bgr, pad, scale, bias, d_target=out.data_ptr(), target_pictures=n)
+        try:
+            if n:
+                self.decode(stream_handle, order, sink=sink, output=output, rotate=rotate, aspect=aspect, color=color, trim=trim, tensor=True)
+        finally:
+            self.set_tensor(clear=True)
+        return out, ok
+
     def decode(self, stream_handle, order, wanted=None, want_rgb=False, sink=None, output=None, jpeg=None, restart_mcus=0,
-               score=False, rotate=None, png=False, aspect=False, color=None, bars=None, trim=False, hist=False):
+               score=False, rotate=None, png=False, aspect=False, color=None, bars=None, trim=False, hist=False, tensor=False):
         """sink(seq, idr, rc, err, params, yuv ndarray | None, rgb ndarray | None) -> 1 accept / 0 reject / -1 stop /
         2 accept and keep until release_picture(seq); the arrays are views of page-locked memory valid only during the call
         (or until the release).  Returns (rc, stats dict).
@@ -905,13 +1059,19 @@ class Engine:
         trim=True: MVHP_OUTPUT_TRIM -- the crop of every picture is trimmed to the box the stream carries (stream_set_trim())
         where the trim rule accepts it; implies the crop.
         hist=True: MVHP_OUTPUT_HIST -- the sink is called as for `output` and reads its picture's plane histograms with
-        picture_hist(seq); the pictures are the same bytes.  Not together with bars."""
+        picture_hist(seq); the pictures are the same bytes.  Not together with bars.
+        tensor=True: MVHP_OUT_TENSOR -- the RGB `output`, rotate, aspect, color and trim deliver is packed into the tensors of
+        set_tensor() on the device and only those come back: sink(seq, idr, rc, err, params, geometry, None, the tensor's bytes
+        as a uint8 array) -- or, with set_tensor(d_target=...), nothing comes back and the last argument is None too.  Not
+        together with jpeg, png or bars (ValueError)."""
         order = (C.c_int * len(order))(*order)
         st = DecodeStats()
         n_wanted = len(order) if wanted is None else wanted
         if png and jpeg is not None:
             raise ValueError("png and jpeg are two output kinds: a call delivers one")
         probe = bars is not None and bars is not False
+        if tensor and (jpeg is not None or png or probe):
+            raise ValueError("tensor, jpeg, png and bars all use the geometry word that carries a length: a call delivers one")
         if probe:
             level = BARS_LEVEL_DEFAULT if bars is True else int(bars)
             if not 1 <= level <= 254:
@@ -922,7 +1082,7 @@ class Engine:
                 raise ValueError("bars needs a sink: the boxes are delivered with the geometry")
             if hist:
                 raise ValueError("bars and hist are two probes: a call runs one")
-        if output is not None or jpeg is not None or score or rotate is not None or png or aspect or color is not None or probe or trim or hist:
+        if output is not None or jpeg is not None or score or rotate is not None or png or aspect or color is not None or probe or trim or hist or tensor:
             req = output_request(output, rotate, aspect, color, trim=bool(trim)) or OutputRequest(0, 0, 0, 0)
             if score:
                 req.flags |= OUTPUT_SCORE
@@ -939,12 +1099,12 @@ class Engine:
                     return 1 if rc == SUCCESS else 0
                 pr, geom = p.contents, OutputGeometry.from_buffer_copy(g.contents)
                 y = np.ctypeslib.as_array(yuv, shape=(geom.yuv_bytes,)) if yuv else None
-                r = np.ctypeslib.as_array(rgb, shape=(geom.reserved[0] if jpeg is not None or png else geom.rgb_bytes,)) if rgb else None
+                r = np.ctypeslib.as_array(rgb, shape=(geom.reserved[0] if jpeg is not None or png or tensor else geom.rgb_bytes,)) if rgb else None
                 return int(sink(seq, idr, rc, err.decode() if err else "", pr, geom, y, r))
 
             cbx = SINK_EX_T(_cbx) if sink is not None else C.cast(None, SINK_EX_T)
             rc = self._L.mvhp_engine_decode_ex(self._h, stream_handle, order, len(order), n_wanted,
-                                               OUT_JPEG if jpeg is not None else OUT_PNG if png else int(want_rgb), C.byref(req), cbx, None, C.byref(st))
+                                               OUT_JPEG if jpeg is not None else OUT_PNG if png else OUT_TENSOR if tensor else int(want_rgb), C.byref(req), cbx, None, C.byref(st))
             return rc, st.as_dict()
 
         def _cb(user, seq, idr, rc, err, p, yuv, rgb):

@@ -4,13 +4,15 @@
 // lets the sink check that the right picture arrives in the right place, in order, through chunks, batches, several
 // contexts and a re-queue.  Nothing here is part of libminivideo.so.
 //
-// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes> [jpeg | png | score | bars | hist | orient | color <stream whose SPS VUI changes>]]]
+// usage: engine_harness <stream.264> [<stream with a broken picture> <its index> [<stream whose SPS crop changes> [jpeg | png | score | bars | hist | tensor | orient | color <stream whose SPS VUI changes>]]]
 // The fourth argument adds the geometry mode: mvhp_engine_decode_ex and minivideo_decode under MINIVIDEO_CROP /
 // MINIVIDEO_THUMBNAIL against the stub's resample targets.  A fifth argument adds the JPEG mode (MVHP_OUT_JPEG), the PNG mode (MVHP_OUT_PNG against the stub's PNG operation) or the
 // score mode (MVHP_OUTPUT_SCORE against the stub's picture scores, which sum the stub's coded planes on the CPU), or the orient
 // mode (MVHP_OUTPUT_ORIENT / MVHP_OUTPUT_ROTATE and MINIVIDEO_ROTATE against the stub's turn), or the color mode (MVHP_OUTPUT_ASPECT /
 // MVHP_OUTPUT_COLOR, MINIVIDEO_ASPECT and MINIVIDEO_COLOR against the stub's colour pass; a sixth argument names a stream whose
-// SPSs alternate between two VUIs that differ in matrix and range only, so that the colour setting changes and no geometry does).
+// SPSs alternate between two VUIs that differ in matrix and range only, so that the colour setting changes and no geometry does),
+// or the tensor mode (MVHP_OUT_TENSOR and mvhp_engine_set_tensor against the stub's tensor operation: host delivery, and device
+// delivery into a stand-in target in host memory).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -30,6 +32,7 @@
 #include "decode_engine.h"
 #include "png_format.h"
 #include "represent_policy.h"
+#include "tensor_policy.h"
 #include "minivideo.h"
 #include "stream_internal.h"
 
@@ -183,6 +186,13 @@ mvhp_plane_hist_t expected_hist(uint64_t h, bool pattern, const mvhp_stream_para
 //   otherwise; no output planes), and every picture gets a "file" of 64 + checksum % (the longest file - 64) bytes of 0x3d that
 //   starts with bytes 8-15 of that RGB (the checksum) and ends in 0x7a; the blob must be n x the longest file rounded to 16, so
 //   no picture is too big.
+// * tensors (tensor mode): never beside JPEG, PNG or black bars; the RGB the operation reads must be there (the fused RGB of a batch
+//   of the coded size, a pass's target otherwise) and src_w x src_h must be its size; a host slot table must come with its device
+//   twin, to which it is copied first; every picture whose slot is not negative gets a "tensor" of mvhp_tensor_bytes at that
+//   slot of tensor_out: 0x3e, bytes 8-15 of that RGB (the checksum) in bytes 0-7, tensor_tag() in byte 8, 0x7c last.
+constexpr uint8_t kLastTensor = 0x7c;
+std::atomic<int> g_tensor_calls{0};
+uint8_t tensor_tag(const mvhp_tensor_params_t &t) { return (uint8_t)(0x80 | t.dtype << 4 | t.layout << 1 | (t.flags & 1)); }
 constexpr uint8_t kLastYuv = 0x77, kLastRgb = 0x78, kLastJpeg = 0x79, kLastPng = 0x7a, kLastColor = 0x7b;
 std::atomic<int> g_jpeg_calls{0}, g_stats_calls{0}, g_orient_calls{0}, g_mid_calls{0}, g_png_calls{0}, g_color_calls{0};
 std::atomic<int> g_bars_calls{0}, g_bars_level{0}, g_hist_calls{0};
@@ -248,6 +258,14 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
                    rect.crop_x + rect.crop_w > p->width_mbs * 16 || rect.crop_y + rect.crop_h > p->height_mbs * 16)) {
         err = "stub: plane-histogram launch without buffers or rectangle";
         return MVHP_FAILURE;
+    }
+    if (j.tensor) {
+        const uint32_t sw = g ? g->out_w : p->width_mbs * 16, sh = g ? g->out_h : p->height_mbs * 16;
+        if (j.jpeg || j.png || j.bars || !j.tensor_out || ((uintptr_t)j.tensor_out & 15) || !(resample ? j.out_rgb : j.d_rgb) || j.tensor->src_w != sw ||
+            j.tensor->src_h != sh || !mvtensor::bytes(*j.tensor) || !mvtensor::finite(*j.tensor) || (j.slots_host != nullptr) != (j.d_slots != nullptr)) {
+            err = "stub: tensor launch without buffers or parameters";
+            return MVHP_FAILURE;
+        }
     }
     if (g && g->crop_x == g_watch_crop[0] && g->crop_y == g_watch_crop[1] && g->crop_w == g_watch_crop[2] && g->crop_h == g_watch_crop[3]) g_watch_hits++;
     for (int i = 0; i < n; i++)
@@ -316,6 +334,19 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
             j.stats[i] = st;
         }
         if (j.bars) j.bars[i] = expected_bars(h, &rect);
+        if (j.tensor) {
+            if (i == 0 && j.slots_host) memcpy(j.d_slots, j.slots_host, (size_t)n * sizeof(int32_t));
+            const int32_t slot = j.d_slots ? j.d_slots[i] : i;
+            if (slot >= 0) {
+                const size_t tb = mvtensor::bytes(*j.tensor);
+                const uint8_t *src = resample ? j.out_rgb + (size_t)i * gr : j.d_rgb + (size_t)i * rb;
+                uint8_t *t = (uint8_t *)j.tensor_out + (size_t)slot * tb;
+                memset(t, 0x3e, tb);
+                memcpy(t, src + 8, 8);
+                t[8] = tensor_tag(*j.tensor);
+                t[tb - 1] = kLastTensor;
+            }
+        }
         if (j.hist) {
             mvhp_plane_hist_t r{};
             const size_t Wp = (size_t)p->width_mbs * 16, Hp = (size_t)p->height_mbs * 16;
@@ -339,12 +370,13 @@ int stub_run_batch(DevCtx *, const mvengine::BatchJob &j, mvengine::BatchDone &d
     if (j.stats) g_stats_calls++;
     if (j.bars) { g_bars_calls++; g_bars_level = j.bars_level; }
     if (j.hist) g_hist_calls++;
+    if (j.tensor) g_tensor_calls++;
     return MVHP_SUCCESS;
 }
 
 mvengine::DeviceApi g_stub = {stub_device_count, stub_host_alloc, stub_host_free, stub_ctx_create, stub_ctx_destroy,
                                     stub_dev_alloc, stub_dev_free, stub_dev_free_bytes, stub_copy_n, stub_copy_n, stub_run_batch,
-                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_PNG | mvengine::CAP_COLOR | mvengine::CAP_BARS | mvengine::CAP_HIST,
+                                    mvengine::CAP_GEOMETRY | mvengine::CAP_JPEG | mvengine::CAP_SCORE | mvengine::CAP_ORIENT | mvengine::CAP_PNG | mvengine::CAP_COLOR | mvengine::CAP_BARS | mvengine::CAP_HIST | mvengine::CAP_TENSOR,
                                     nullptr, nullptr};   // (no placed arena on the stub device)
 
 uint64_t picture_checksum(const mvhp_stream &s, int idr)
@@ -2225,6 +2257,250 @@ int main(int argc, char **argv)
                 unsetenv("MINIVIDEO_REPRESENTATIVE");
             }
             printf("HIST MODE DONE\n");
+        }
+        if (argc > 5 && !strcmp(argv[5], "tensor")) {   // ---- tensor mode: MVHP_OUT_TENSOR against the stub's tensor operation ----
+            std::vector<int> order;
+            for (int k = 0; k < 3 * n3; k++) order.push_back(k % n3);
+            // sink: the right picture, in order, its geometry that of the request, no planes; host delivery: the stub's tensor of
+            // the picture's own RGB, of exactly the length g->reserved[0] names; device delivery: nothing comes, and the tensor
+            // stands in its slot of the target by the time the sink runs
+            struct CheckT {
+                const mvhp_stream *s = nullptr;
+                mvhp_output_request_t req{};
+                mvhp_tensor_request_t treq{};
+                std::vector<int> order;
+                const uint8_t *target = nullptr;
+                size_t slot_bytes = 0;
+                int calls = 0, ok = 0, failed = 0, bad = 0, next_seq = 0, past_target = 0, no_canvas = 0;
+                uint64_t bytes = 0;
+                std::vector<int> delivered;
+                static int sink(void *user, int seq, int idr, int rc, const char *err, const mvhp_stream_params_t *, const mvhp_output_geometry_t *g,
+                                const uint8_t *yuv, const uint8_t *rgb)
+                {
+                    CheckT &c = *static_cast<CheckT *>(user);
+                    c.calls++;
+                    if (seq != c.next_seq || idr != c.order[(size_t)seq] || !g) c.bad++;
+                    c.next_seq = seq + 1;
+                    if (rc != MVHP_SUCCESS) {
+                        c.failed++;
+                        if (!err || !*err || yuv || rgb) c.bad++;
+                        if (err && strstr(err, "slots")) c.past_target++;
+                        if (err && strstr(err, "canvas")) c.no_canvas++;
+                        return 0;
+                    }
+                    mvhp_output_geometry_t want, got = *g;
+                    got.reserved[0] = got.reserved[1] = 0;   // (the tensor's length; the score, where the call asks for it)
+                    if (mvhp_output_geometry(c.s, idr, &c.req, &want) != MVHP_SUCCESS || memcmp(&want, &got, sizeof(want)) != 0) { c.bad++; return 0; }
+                    const mvhp_tensor_params_t t = mvtensor::of_request(c.treq, g->out_w, g->out_h);
+                    const size_t tb = mvtensor::bytes(t);
+                    if (!tb || g->reserved[0] != tb || yuv || (rgb != nullptr) != (c.target == nullptr)) { c.bad++; return 0; }
+                    if (c.target && tb != c.slot_bytes) { c.bad++; return 0; }
+                    const uint8_t *ten = c.target ? c.target + (size_t)seq * tb : rgb;
+                    const uint64_t h = picture_checksum(*c.s, idr);
+                    uint64_t stamp = 0;
+                    memcpy(&stamp, ten, 8);
+                    if (stamp != h || ten[8] != tensor_tag(t) || ten[9] != 0x3e || ten[tb - 1] != kLastTensor) c.bad++;
+                    c.bytes += tb;
+                    c.ok++;
+                    c.delivered.push_back(seq);
+                    return 1;
+                }
+            };
+            auto tensor_request = [](uint32_t cw, uint32_t ch, uint32_t dtype, uint32_t layout, uint32_t flags) {
+                mvhp_tensor_request_t t{};
+                t.canvas_w = cw; t.canvas_h = ch; t.dtype = dtype; t.layout = layout; t.flags = flags; t.pad_rgb = 0x102030;
+                for (int k = 0; k < 3; k++) { t.scale[k] = 1.0f / 255.0f; t.bias[k] = -0.5f * (float)k; }
+                return t;
+            };
+            auto run_tensor = [&](const char *name, mvhp_engine_opts_t o, const mvhp_stream &st, const std::vector<int> &ord, mvhp_output_request_t req,
+                                  const mvhp_tensor_request_t &treq, uint32_t extra, CheckT &c, mvhp_decode_stats_t &stats) {
+                mvhp_engine_t *e = nullptr;
+                if (mvhp_engine_create(&o, &e) != MVHP_SUCCESS) { failures++; return MVHP_FAILURE; }
+                c.s = &st; c.req = req; c.treq = treq; c.order = ord;
+                c.target = (const uint8_t *)treq.d_target;
+                EXPECT(mvhp_engine_set_tensor(e, &treq) == MVHP_SUCCESS);
+                req.flags |= extra;
+                const int rc = mvhp_engine_decode_ex(e, &st, ord.data(), (int)ord.size(), (int)ord.size(), MVHP_OUT_TENSOR, &req, CheckT::sink, &c, &stats);
+                mvhp_engine_destroy(e);
+                printf("%-28s rc=%d contexts=%d flags=%#x ok=%u failed=%u batches=%u geometry=%u requeued=%u d2h=%llu\n", name, rc, o.contexts, req.flags,
+                       stats.pictures_ok, stats.pictures_failed, stats.batches, stats.geometry_launches, stats.batches_requeued,
+                       (unsigned long long)stats.d2h_bytes);
+                return rc;
+            };
+            int formed_crop = 0;
+            for (int idr : order) { mvhp_output_geometry_t g; formed_crop += mvhp_output_geometry(&s3, idr, &crop, &g) == MVHP_SUCCESS; }
+            // ---- host delivery: one to three contexts, large and small batches, the coded size, cropped, boxed onto a fixed canvas
+            int combo = 0;
+            for (int contexts = 1; contexts <= 3; contexts++)
+                for (int batch : {64, 3})
+                    for (mvhp_output_request_t req : {mvhp_output_request_t{0, 0, 0, 0}, crop, box})
+                        for (uint32_t extra : {0u, (uint32_t)MVHP_OUTPUT_SCORE}) {
+                            mvhp_engine_opts_t o = base; o.contexts = contexts; o.chunk_pictures = 2; o.batch_pictures = batch;
+                            o.fail_context = contexts == 3 ? 0 : -1;   // (three contexts: context 0's first batch fails and is re-queued)
+                            const bool boxed = (req.flags & MVHP_OUTPUT_BOX) != 0;
+                            const mvhp_tensor_request_t treq = tensor_request(boxed ? 48 : 0, boxed ? 48 : 0, (uint32_t)(combo % 3), (uint32_t)(combo / 3 % 2), (uint32_t)(combo / 6 % 2));
+                            combo++;
+                            const int calls0 = g_tensor_calls, stats0 = g_stats_calls;
+                            CheckT c; mvhp_decode_stats_t st;
+                            EXPECT(run_tensor(boxed ? "tensor box, host" : req.flags ? "tensor crop, host" : "tensor coded size, host", o, s3, order, req, treq,
+                                              extra, c, st) == MVHP_SUCCESS);
+                            EXPECT(c.bad == 0 && c.calls == (int)order.size() && c.ok == (int)st.pictures_ok && c.ok == (req.flags ? formed_crop : (int)order.size()));
+                            EXPECT(st.d2h_bytes == c.bytes + (extra ? 32ull * (uint64_t)c.ok : 0ull));   // the tensors (and the scores), nothing else
+                            EXPECT(g_tensor_calls - calls0 == (int)st.batches && g_stats_calls - stats0 == (extra ? (int)st.batches : 0));
+                            EXPECT((int)st.batches_requeued == (contexts == 3 ? 1 : 0));
+                            if (!req.flags) EXPECT(st.geometry_launches == 0);
+                        }
+            {   // a picture larger than the canvas fails in its place with a message; the others are delivered
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 4;
+                CheckT c; mvhp_decode_stats_t st;
+                EXPECT(run_tensor("tensor: canvas too small", o, s3, order, box, tensor_request(32, 48, MVHP_TENSOR_F16, MVHP_TENSOR_NCHW, 0), 0, c, st) == MVHP_FAILURE);
+                EXPECT(c.bad == 0 && c.ok == 0 && c.no_canvas == formed_crop && formed_crop > 0);
+            }
+            // ---- device delivery into a stand-in target in host memory, one context
+            auto aligned = [](std::vector<uint8_t> &v) { return v.data() + ((16 - ((uintptr_t)v.data() & 15)) & 15); };
+            for (int batch : {64, 3}) {
+                mvhp_engine_opts_t o = base; o.contexts = 1; o.chunk_pictures = 2; o.batch_pictures = batch;
+                mvhp_tensor_request_t treq = tensor_request(48, 48, MVHP_TENSOR_BF16, MVHP_TENSOR_NHWC, MVHP_TENSOR_BGR);
+                const size_t tb = 3 * 48 * 48 * 2;
+                const int slots = (int)order.size() - 2;   // the last two pictures have no slot
+                std::vector<uint8_t> mem((size_t)order.size() * tb + 16, 0xee);
+                treq.d_target = aligned(mem);
+                treq.target_pictures = (uint32_t)slots;
+                CheckT c; c.slot_bytes = tb; mvhp_decode_stats_t st;
+                const int calls0 = g_tensor_calls;
+                EXPECT(run_tensor("tensor box, device", o, s3, order, box, treq, 0, c, st) == MVHP_SUCCESS);
+                EXPECT(c.bad == 0 && c.calls == (int)order.size() && c.ok == (int)st.pictures_ok && c.ok > 0 && st.d2h_bytes == 0);
+                EXPECT(c.past_target >= 1 && c.past_target <= 2 && g_tensor_calls - calls0 == (int)st.batches);
+                std::vector<bool> got(order.size(), false);
+                for (int seq : c.delivered) got[(size_t)seq] = true;
+                for (size_t k = 0; k < order.size(); k++) {   // a failed picture's slot (and the room past the last slot) is untouched
+                    if (got[k]) { EXPECT((int)k < slots); continue; }
+                    const uint8_t *t = aligned(mem) + k * tb;
+                    bool same = true;
+                    for (size_t i = 0; i < tb; i++) same = same && t[i] == 0xee;
+                    EXPECT(same);
+                }
+            }
+            {   // a picture that fails to parse, in the middle of a batch: its slot stays as it was (canvas 0: slots of the pictures' size)
+                std::vector<uint8_t> b2 = read_file(argv[2]);
+                const int broken = atoi(argv[3]);
+                mvhp_stream s2;
+                s2.data = b2.data();
+                s2.size = b2.size();
+                EXPECT(s2.build(err) == h264::RC_SUCCESS);
+                std::vector<int> o2(s2.idrs.size());
+                for (size_t i = 0; i < o2.size(); i++) o2[i] = (int)i;
+                mvhp_stream_params_t p2;
+                EXPECT(mvhp_stream_params(&s2, 0, &p2) == MVHP_SUCCESS);
+                mvhp_engine_opts_t o = base; o.contexts = 1; o.chunk_pictures = 3; o.batch_pictures = 6;
+                mvhp_tensor_request_t treq = tensor_request(0, 0, MVHP_TENSOR_F32, MVHP_TENSOR_NCHW, 0);
+                const size_t tb = (size_t)p2.width_mbs * p2.height_mbs * 768 * 4;
+                std::vector<uint8_t> mem(o2.size() * tb + 16, 0xee);
+                treq.d_target = aligned(mem);
+                treq.target_pictures = (uint32_t)o2.size();
+                CheckT c; c.slot_bytes = tb; mvhp_decode_stats_t st;
+                EXPECT(run_tensor("tensor, device, broken", o, s2, o2, mvhp_output_request_t{0, 0, 0, 0}, treq, 0, c, st) == MVHP_SUCCESS);
+                EXPECT(c.bad == 0 && c.failed == 1 && c.ok == (int)o2.size() - 1 && st.d2h_bytes == 0);
+                const uint8_t *t = aligned(mem) + (size_t)broken * tb;
+                bool same = true;
+                for (size_t i = 0; i < tb; i++) same = same && t[i] == 0xee;
+                EXPECT(same);
+            }
+            {   // ---- refusals, each with a message and before any launch
+                struct Refused { const char *name; int contexts; bool set, device; int mask; uint32_t flags; bool plain_sink; const char *word; };
+                std::vector<uint8_t> mem(64, 0xee);
+                for (const Refused &r : {Refused{"tensor: no request", 1, false, false, MVHP_OUT_TENSOR, 0, false, "mvhp_engine_set_tensor"},
+                                         Refused{"tensor with JPEG", 1, true, false, MVHP_OUT_TENSOR | MVHP_OUT_JPEG, 0, false, "MVHP_OUT_JPEG"},
+                                         Refused{"tensor with PNG", 1, true, false, MVHP_OUT_TENSOR | MVHP_OUT_PNG, 0, false, "MVHP_OUT_PNG"},
+                                         Refused{"tensor with bars", 1, true, false, MVHP_OUT_TENSOR, MVHP_OUTPUT_BARS, false, "MVHP_OUTPUT_BARS"},
+                                         Refused{"tensor, plain sink", 1, true, false, MVHP_OUT_TENSOR, 0, true, "mvhp_engine_decode_ex"},
+                                         Refused{"tensor, device, 2 contexts", 2, true, true, MVHP_OUT_TENSOR, 0, false, "one context"}}) {
+                    mvhp_engine_opts_t o = base; o.contexts = r.contexts;
+                    std::string why;
+                    mvengine::Engine *pe = mvengine::engine_create(g_stub, &o, why);
+                    EXPECT(pe != nullptr);
+                    mvhp_tensor_request_t treq = tensor_request(48, 48, MVHP_TENSOR_F16, MVHP_TENSOR_NCHW, 0);
+                    if (r.device) { treq.d_target = aligned(mem); treq.target_pictures = 1; }
+                    if (r.set) EXPECT(pe && mvengine::engine_set_tensor(pe, &treq, why) == MVHP_SUCCESS);
+                    const int launches0 = g_recon_calls + g_geometry_calls + g_jpeg_calls + g_png_calls + g_tensor_calls;
+                    mvhp_output_request_t req{r.flags, 0, 0, 0};
+                    CheckT c; c.s = &s3; c.order = order; mvhp_decode_stats_t st;
+                    Check cp; cp.s = &s3; cp.order = order;
+                    const int rc = !pe ? MVHP_SUCCESS
+                                   : r.plain_sink ? mvengine::engine_decode(pe, s3, order.data(), (int)order.size(), (int)order.size(), r.mask, nullptr, Check::sink, nullptr, &cp, &st, why)
+                                                  : mvengine::engine_decode(pe, s3, order.data(), (int)order.size(), (int)order.size(), r.mask, &req, nullptr, CheckT::sink, &c, &st, why);
+                    printf("%-28s rc=%d message: %s\n", r.name, rc, why.c_str());
+                    EXPECT(rc == MVHP_FAILURE && c.calls == 0 && cp.calls == 0 && why.find(r.word) != std::string::npos);
+                    EXPECT(g_recon_calls + g_geometry_calls + g_jpeg_calls + g_png_calls + g_tensor_calls == launches0);
+                    if (pe && r.set) {   // taking the request back: the call is refused again
+                        EXPECT(mvengine::engine_set_tensor(pe, nullptr, why) == MVHP_SUCCESS);
+                        const mvhp_output_request_t none{0, 0, 0, 0};
+                        EXPECT(mvengine::engine_decode(pe, s3, order.data(), (int)order.size(), (int)order.size(), MVHP_OUT_TENSOR, &none, nullptr, CheckT::sink, &c, &st, why) == MVHP_FAILURE);
+                        EXPECT(why.find("mvhp_engine_set_tensor") != std::string::npos && c.calls == 0);
+                    }
+                    mvengine::engine_destroy(pe);
+                }
+                // malformed requests
+                mvhp_engine_opts_t o = base; o.contexts = 1;
+                std::string why;
+                mvengine::Engine *pe = mvengine::engine_create(g_stub, &o, why);
+                EXPECT(pe != nullptr);
+                int n_bad = 0;
+                for (int k = 0; pe && k < 9; k++) {
+                    mvhp_tensor_request_t t = tensor_request(48, 48, MVHP_TENSOR_F16, MVHP_TENSOR_NCHW, 0);
+                    if (k == 0) t.dtype = 3;
+                    if (k == 1) t.layout = 2;
+                    if (k == 2) t.flags = 2;
+                    if (k == 3) t.canvas_w = 0;
+                    if (k == 4) t.canvas_h = 16385;
+                    if (k == 5) t.scale[1] = INFINITY;
+                    if (k == 6) t.reserved = 1;
+                    if (k == 7) { t.d_target = aligned(mem) + 8; t.target_pictures = 1; }
+                    if (k == 8) { t.d_target = aligned(mem); t.target_pictures = 0; }
+                    const int rc = mvengine::engine_set_tensor(pe, &t, why);
+                    printf("%-28s %d rc=%d message: %s\n", "malformed tensor request", k, rc, why.c_str());
+                    EXPECT(rc == MVHP_FAILURE && why.find("mvhp_engine_set_tensor") != std::string::npos);
+                    n_bad += rc == MVHP_FAILURE;
+                }
+                EXPECT(n_bad == 9);
+                mvengine::engine_destroy(pe);
+                EXPECT(mvhp_engine_set_tensor(nullptr, nullptr) == MVHP_FAILURE && mvhp_engine_contexts(nullptr) == 0);
+            }
+            {   // a device table without the operation: the call fails with the message before any launch; other calls are not affected
+                g_stub.caps &= ~mvengine::CAP_TENSOR;
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 4;
+                std::string why;
+                mvengine::Engine *pe = mvengine::engine_create(g_stub, &o, why);
+                EXPECT(pe != nullptr);
+                const mvhp_tensor_request_t treq = tensor_request(0, 0, MVHP_TENSOR_F16, MVHP_TENSOR_NCHW, 0);
+                EXPECT(pe && mvengine::engine_set_tensor(pe, &treq, why) == MVHP_SUCCESS);
+                const int launches0 = g_recon_calls + g_geometry_calls + g_tensor_calls;
+                CheckT c; c.s = &s3; c.order = order; mvhp_decode_stats_t st;
+                mvhp_output_request_t req = crop;
+                const int rc = pe ? mvengine::engine_decode(pe, s3, order.data(), (int)order.size(), (int)order.size(), MVHP_OUT_TENSOR, &req, nullptr, CheckT::sink, &c, &st, why) : MVHP_SUCCESS;
+                printf("%-28s rc=%d message: %s\n", "tensor: table without it", rc, why.c_str());
+                EXPECT(rc == MVHP_FAILURE && c.calls == 0 && why.find("tensor operation") != std::string::npos);
+                EXPECT(g_recon_calls + g_geometry_calls + g_tensor_calls == launches0);
+                mvengine::engine_destroy(pe);
+                CheckG cg;
+                EXPECT(run_ex("tensor: table without it, off", o, s3, order, MVHP_OUT_RGB_ONLY, crop, cg, st) == MVHP_SUCCESS && cg.bad == 0);
+                g_stub.caps |= mvengine::CAP_TENSOR;
+            }
+            {   // without MVHP_OUT_TENSOR a set request changes nothing: the same pictures, the operation never called
+                mvhp_engine_opts_t o = base; o.contexts = 2; o.chunk_pictures = 2; o.batch_pictures = 4;
+                mvhp_engine_t *e = nullptr;
+                EXPECT(mvhp_engine_create(&o, &e) == MVHP_SUCCESS);
+                const mvhp_tensor_request_t treq = tensor_request(48, 48, MVHP_TENSOR_F16, MVHP_TENSOR_NCHW, 0);
+                EXPECT(mvhp_engine_set_tensor(e, &treq) == MVHP_SUCCESS && mvhp_engine_contexts(e) == 2);
+                const int calls0 = g_tensor_calls;
+                CheckG cg; cg.s = &s3; cg.req = box; cg.order = order; cg.want_rgb = true; cg.want_yuv = false;
+                mvhp_decode_stats_t st;
+                EXPECT(mvhp_engine_decode_ex(e, &s3, order.data(), (int)order.size(), (int)order.size(), MVHP_OUT_RGB_ONLY, &box, CheckG::sink, &cg, &st) == MVHP_SUCCESS);
+                EXPECT(cg.bad == 0 && g_tensor_calls == calls0 && st.d2h_bytes == d2h_expected(s3, order, box, MVHP_OUT_RGB_ONLY));
+                printf("%-28s ok=%u d2h=%llu\n", "tensor: request set, flag off", st.pictures_ok, (unsigned long long)st.d2h_bytes);
+                mvhp_engine_destroy(e);
+            }
+            printf("TENSOR MODE DONE\n");
         }
         if (argc > 5 && !strcmp(argv[5], "bars")) {   // ---- bars mode: MVHP_OUTPUT_BARS / MVHP_OUTPUT_TRIM against the stub's black-bar operation ----
             std::vector<int> order;
